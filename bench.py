@@ -12,7 +12,8 @@ max-over-ranks of the timed region.  The step itself never touches torch.
 A "step" = one sag_step_device() over the whole shard: action noise + clip, nstep=5
 physics substeps with contact, reward (+ goal resampling), cost, 3x16 lidar, sensors,
 observation write.  Inputs (layouts, actions) are resident in HBM before timing.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step returned (obs, reward, cost,
+done, goal_met of a fixed env sample) as .npy files: the inputs are seeded, so two builds can be compared output for output.
 
 Every `roofline` block names its kernels and is checked against the committed rocprofv3 summary of the SAME device
 sources (profiles/kernels.json, written by tools/prof_summary.py, keyed by `src_sha16`): if that summary is of these
@@ -43,6 +44,9 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # MI355X_MICROARCH.md: fp64 vector (non-matrix) peak
 FP32_VECTOR_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: fp32 vector peak
 N_ACTION_BUFS = 8
+# --dump-outputs: bytes of .npy data written over all ranks (under the 64-MB limit); the env sample is drawn with this seed
+DUMP_BYTES = 48 << 20
+DUMP_SEED = 0
 # per robot: substeps of one env-step (safe_adaptation_gym.py:15-19), the kernels of one step() in the split form and
 # in the single-launch form (below SAG_SPLIT_MIN_ENVS), algorithmic bytes per env-step (None: not HBM-bound)
 ROBOT_LINE = {
@@ -156,8 +160,29 @@ class DeviceRun:
     self.busy_frac = self.ctx.busy_count() / self.envs
     return float(cost.mean()), int(done.sum()), bool(np.isfinite(obs).all())
 
+  def outputs(self):
+    """What the last step() left in its output buffers, as a caller of sag_step_device receives it."""
+    self.ctx.wait()
+    n, dl = self.envs, self.ctx.dev_download
+    return {'obs': dl(self.d_obs, (n, self.ctx.info['obs_dim']), np.float32), 'reward': dl(self.d_rew, (n, 2), np.float32),
+            'cost': dl(self.d_cost, (n,), np.uint8), 'done': dl(self.d_done, (n,), np.uint8),
+            'goal_met': dl(self.d_met, (n,), np.uint8)}
+
   def close(self):
     self.ctx.close()
+
+
+def dump_outputs(outs, env0, out_dir, budget, suffix=''):
+  """--dump-outputs: outs {name: [envs, ...] array} -> out_dir/<name><suffix>.npy in float32, rows of a fixed seeded sample
+  of the envs when all of them would exceed `budget` bytes, and the global ids of those rows (env_id<suffix>.npy, float64)."""
+  envs = len(next(iter(outs.values())))
+  per_env = 8 + sum(4 * int(np.prod(a.shape[1:])) for a in outs.values())
+  keep = min(envs, budget // per_env)
+  idx = np.arange(envs) if keep == envs else np.sort(np.random.RandomState(DUMP_SEED).choice(envs, keep, replace=False))
+  os.makedirs(out_dir, exist_ok=True)
+  np.save(os.path.join(out_dir, f'env_id{suffix}.npy'), (env0 + idx).astype(np.float64))
+  for name, a in outs.items():
+    np.save(os.path.join(out_dir, f'{name}{suffix}.npy'), a[idx].astype(np.float32))
 
 
 def timed(run, steps, warmup, barrier):
@@ -306,6 +331,8 @@ def main(argv=None, run_factory=None, emit=print):
   ap.add_argument('--no-c4', action='store_true', help='skip the sharded Doggo / multitask line (BASELINE config 4)')
   ap.add_argument('--c4-envs', type=int, default=4096, help='Doggo envs per GPU of the config-4 line')
   ap.add_argument('--c4-steps', type=int, default=30)
+  ap.add_argument('--dump-outputs', metavar='DIR', help='write what the headline step() returned in its last timed step to '
+                  'DIR/<name>.npy (float32; a fixed seeded sample of the envs, <= 48 MB in all; with N ranks: <name>.rank<r>.npy)')
   args = ap.parse_args(argv)
 
   rank = int(os.environ.get('RANK', '0'))
@@ -367,6 +394,8 @@ def main(argv=None, run_factory=None, emit=print):
   k_ms = max_over_ranks(k_ms_rank)            # the roofline is quoted on the slowest rank's kernel time
   k_ms_per_rank = gather_ranks(k_ms_rank)
   cost_rate, n_done, finite = run.stats()
+  if args.dump_outputs:
+    dump_outputs(run.outputs(), rank * args.envs, args.dump_outputs, DUMP_BYTES // world, '' if world == 1 else f'.rank{rank}')
   total_env_steps = world * args.envs * args.steps
   value = total_env_steps / elapsed
   line = ROBOT_LINE[args.robot]

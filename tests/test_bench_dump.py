@@ -1,0 +1,82 @@
+"""bench.py --dump-outputs on a CPU stand-in for DeviceRun: what is written is the last timed step's output, --steps sets
+the number of timed steps, the env sample is fixed and within the byte budget.  The harness is tested, not the kernel."""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+
+class CountingRun:
+  """DeviceRun's interface; the outputs of a step are a function of (env, steps taken so far)."""
+
+  def __init__(self, task, envs, device, rank, robot='point'):
+    self.envs, self.t = envs, 0
+
+  def burn_in(self, steps):
+    self.run(steps)
+
+  def run(self, steps):
+    self.t += steps
+
+  def wait(self):
+    pass
+
+  def timing(self, on):
+    pass
+
+  def kernel_time_ms(self):
+    return 1.0, self.t
+
+  def stats(self):
+    return 0.0, 0, True
+
+  def outputs(self):
+    e = np.arange(self.envs, dtype=np.float32)
+    return {'obs': e[:, None] * 100 + np.arange(60, dtype=np.float32) + self.t * 1e-2,
+            'reward': np.stack([e, -e], 1) + self.t, 'cost': (np.arange(self.envs) % 2).astype(np.uint8),
+            'done': np.zeros(self.envs, np.uint8), 'goal_met': np.full(self.envs, self.t % 256, np.uint8)}
+
+  def close(self):
+    pass
+
+
+def _bench(out_dir, envs, steps):
+  lines = []
+  bench.main(['--steps', str(steps), '--warmup', '3', '--burn-in', '2', '--envs', str(envs), '--no-c2', '--no-c4',
+              '--no-cpu-baseline', '--dump-outputs', str(out_dir)], run_factory=CountingRun, emit=lines.append)
+  assert len(lines) == 1
+  return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(out_dir, f)) for f in os.listdir(out_dir)}
+
+
+def _last_step(envs, steps):
+  ref = CountingRun('go_to_goal', envs, 0, 0)
+  ref.run(2 + 3 + steps)   # burn-in + warmup + --steps
+  return ref.outputs()
+
+
+def test_dump_is_the_last_timed_step(tmp_path):
+  res, d = _bench(tmp_path, 500, 7)
+  assert res['steps'] == 7
+  assert set(d) == {'env_id', 'obs', 'reward', 'cost', 'done', 'goal_met'}
+  assert d['env_id'].dtype == np.float64 and all(d[k].dtype == np.float32 for k in d if k != 'env_id')
+  np.testing.assert_array_equal(d['env_id'], np.arange(500))   # 500 envs fit the budget: no sampling
+  for k, a in _last_step(500, 7).items():
+    np.testing.assert_array_equal(d[k], a.astype(np.float32))
+
+
+def test_dump_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
+  monkeypatch.setattr(bench, 'DUMP_BYTES', 64 << 10)
+  _, a = _bench(tmp_path / 'a', 5000, 4)
+  _, b = _bench(tmp_path / 'b', 5000, 4)
+  ids = a['env_id']
+  assert 0 < len(ids) < 5000 and np.all(np.diff(ids) > 0) and ids[-1] < 5000
+  assert sum(x.nbytes for x in a.values()) <= 64 << 10
+  for k in a:
+    np.testing.assert_array_equal(a[k], b[k])
+  for k, x in _last_step(5000, 4).items():
+    np.testing.assert_array_equal(a[k], x[ids.astype(np.int64)].astype(np.float32))
