@@ -241,16 +241,31 @@ class DeviceArray:
     return np.lib.stride_tricks.as_strided(full.reshape(-1)[off:], self.shape, self.strides).copy()
 
 
-def device_pointer(x):
-  """Device pointer of a DeviceArray or of anything that exports __cuda_array_interface__ (a torch / cupy array on the GPU)."""
+def device_pointer(x, shape=None, device=None):
+  """Device pointer of a DeviceArray or of anything that exports __cuda_array_interface__ (a torch / cupy array on the GPU).
+  With `shape`, the array is what a step reads as its actions: float32 ('<f4'), exactly that shape, contiguous and - where
+  the array says which device it lives on - on `device`.  Anything else raises ValueError before a kernel can read it
+  (a float64 tensor would be read as float32 pairs, a short one past its end)."""
   if isinstance(x, DeviceArray):
-    return x.ptr
-  cai = getattr(x, '__cuda_array_interface__', None)
-  if cai is None:
-    raise TypeError(f'{type(x).__name__}: not a device array')
-  if cai.get('strides') not in (None,) and tuple(cai['strides']) != tuple(np.zeros(cai['shape'], np.dtype(cai['typestr'])).strides):
+    typestr, xshape, strides, ptr = x.dtype.str, x.shape, x.strides, x.ptr
+    where = getattr(x.ctx, 'device', None)
+  else:
+    cai = getattr(x, '__cuda_array_interface__', None)
+    if cai is None:
+      raise TypeError(f'{type(x).__name__}: not a device array')
+    typestr, xshape, strides, ptr = cai['typestr'], tuple(cai['shape']), cai.get('strides'), int(cai['data'][0])
+    dev = getattr(x, 'device', None)   # torch.device (.index) / cupy Device (.id); the interface itself names none
+    where = getattr(dev, 'index', getattr(dev, 'id', None))
+  if strides is not None and tuple(strides) != tuple(np.zeros(xshape, np.dtype(typestr)).strides):
     raise ValueError('device actions must be contiguous')
-  return int(cai['data'][0])
+  if shape is not None:
+    if np.dtype(typestr) != np.dtype('<f4'):
+      raise ValueError(f'device actions must be float32 (<f4), not {typestr}')
+    if tuple(xshape) != tuple(shape):
+      raise ValueError(f'device actions of shape {tuple(xshape)}: this shard steps {tuple(shape)}')
+    if device is not None and isinstance(where, int) and where != device:
+      raise ValueError(f'device actions on device {where}: this shard runs on device {device}')
+  return ptr
 
 
 class Context:
@@ -261,6 +276,7 @@ class Context:
                has_box=True):
     self.lib = load()
     self.robot = robot
+    self.device = int(device)
     self.info = robot_info(robot)
     self.n_envs = int(n_envs)
     cfg = _Config(ABI_VERSION, ROBOT_IDS[robot], self.n_envs, device, max_hazards, max_vases,

@@ -245,9 +245,11 @@ class BatchedSafeAdaptationGym:
     else:                          # host actions for the whole batch: split over the shards
       a = np.asarray(action, np.float32).reshape(self.n_envs, self.robot.nu)
       acts = [a[s:e] for s, e in self._ranges]
-    for c, b, a in zip(self._ctx, bufs, acts):
-      if on_device(a):
-        d_act = nat.C.c_void_p(nat.device_pointer(a))
+    ptrs = [nat.device_pointer(a, (e - s, self.robot.nu), c.device) if on_device(a) else None
+            for c, (s, e), a in zip(self._ctx, self._ranges, acts)]   # every shard's actions checked before any launch
+    for c, b, a, p in zip(self._ctx, bufs, acts, ptrs):
+      if p is not None:
+        d_act = nat.C.c_void_p(p)
       else:
         c.dev_upload(b['act'], np.ascontiguousarray(a, np.float32))
         d_act = b['act']

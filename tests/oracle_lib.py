@@ -83,6 +83,7 @@ class Oracle:
     ]
     lib.sago_observe_batch.argtypes = [C.POINTER(OEnv), C.c_int, C.c_int, fp]
     lib.sago_noise.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, fp]
+    lib.sago_noise_ep.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, fp]
     lib.sago_actions.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, fp]
     lib.sago_philox.argtypes = [up, up, up]
     lib.sago_robot_info.argtypes = [C.c_int, ip, dp]
@@ -281,6 +282,22 @@ class Oracle:
     self.lib.sago_noise(key[0], key[1], env_id, step, nu,
                         out.ctypes.data_as(C.POINTER(C.c_float)))
     return out[:nu]
+
+  def noise_ep(self, key, env_id, step, episode, nu):
+    """Throughput mode's action noise of env `env_id` at `step` in episode nonce `episode` (I_EPISODE)."""
+    out = np.zeros(nu + 1, np.float32)
+    self.lib.sago_noise_ep(key[0], key[1], env_id, step, episode, nu,
+                           out.ctypes.data_as(C.POINTER(C.c_float)))
+    return out[:nu]
+
+  def philox(self, ctr, key):
+    """Philox4x32-10 of one 4-word counter under a 2-word key."""
+    c = np.ascontiguousarray(ctr, np.uint32)
+    k = np.ascontiguousarray(key, np.uint32)
+    out = np.zeros(4, np.uint32)
+    up = C.POINTER(C.c_uint32)
+    self.lib.sago_philox(c.ctypes.data_as(up), k.ctypes.data_as(up), out.ctypes.data_as(up))
+    return out
 
   def actions(self, key, env_id, step, nu):
     out = np.zeros(nu + 3, np.float32)

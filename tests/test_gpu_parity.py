@@ -261,6 +261,12 @@ def test_step_lockstep_vs_oracle(nat, oracle, oracle32, robot, task):
   _lockstep(nat, oracle, oracle32, robot, task, int(os.environ.get('SAG_LOCKSTEP_SCALE', '1')))
 
 
+@pytest.mark.parametrize('robot,task', [('point', 'go_to_goal'), ('point', 'catch_goal'), ('point', 'press_buttons'),
+                                        ('point', MIXED), ('car', 'push_box'), ('car', MIXED)])
+def test_step_lockstep_throughput_vs_oracle(nat, oracle, oracle32, robot, task):
+  _lockstep(nat, oracle, oracle32, robot, task, 1, throughput=True)
+
+
 # The soak at its real size (8 x the envs: 1536 envs x 160 steps per case): the two cases that were marginal
 # against the old constant end-to-end lidar bound (car tethered to / pushing the box at < 1 m) and the two
 # multitask mixes
@@ -269,10 +275,50 @@ def test_step_lockstep_soak(nat, oracle, oracle32, robot, task):
   _lockstep(nat, oracle, oracle32, robot, task, 8)
 
 
-def _lockstep(nat, oracle, oracle32, robot, task, scale):
+# Throughput mode (parity_rng=False, make()'s default and what bench.py times): the step kernel draws its action noise
+# (Philox stream 1) and in-step words (stream 0) itself.  A context seed with a non-zero high word: key = (low, high).
+TP_SEED = 0x9E3779B97F4A7C15
+TP_KEY = (TP_SEED & 0xffffffff, TP_SEED >> 32)
+TP_EPISODES = (1, 2**23, 0xfffffe)
+
+
+def _throughput_counters(nat, ctx, n):
+  """Moves part of the batch off the trivial counter before the first step: episode nonces 1, 2^23 and 0xfffffe on
+  three quarters of the envs, the step counter raised by 1000 on every fifth."""
+  rf, ri = ctx.get_state()
+  for k, ep in enumerate(TP_EPISODES):
+    ri[k + 1::4, nat.I_EPISODE] = ep
+  ri[::5, nat.I_STEP] += 1000
+  ctx.set_state(rf, ri)
+  return ctx.get_state()
+
+
+def _oracle_noise(oracle, ri, nu, key=TP_KEY):
+  """The action noise the throughput step of these pre-step records draws (the oracle's sago_noise_ep)."""
+  u32 = lambda v: int(v) & 0xffffffff   # noqa: E731
+  return np.array([oracle.noise_ep(key, u32(r[12]), u32(r[11]), int(r[14]), nu)
+                   for r in ri], np.float32).reshape(len(ri), nu)
+
+
+def _draw_counts(nat, ri, o_met, o_used):
+  """Which in-step draws a throughput step made, from the oracle's words consumed and the pre-step task ints:
+  goal resamples (a goal met in a goal-family task: 4 words per candidate), CatchGoal radius redraws (its 10-step timer
+  expiring) and PressButtons goal-button choices (a goal button pressed)."""
+  task = ri[:, nat.I_TASK]
+  buttons = np.isin(task, [8, 9])                  # press_buttons, press_buttons_scarce
+  resample = o_met.astype(bool) & ~buttons & (task != 1) & (o_used >= 4)   # (collect: no draw)
+  radius = (task == 0) & (ri[:, nat.I_CATCH_TIMER] <= 1) & (o_used >= 2)   # catch_goal
+  button = o_met.astype(bool) & buttons & (o_used >= 1)
+  return np.array([resample.sum(), radius.sum(), button.sum(), o_used.sum()], np.int64)
+
+
+def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
   """Every step: take the device state, advance the device AND both oracle builds (fp64 =
   the specification, fp32 = same source in the device's precision) from it with identical
   action / noise / random tape, compare outputs and next state, continue from the device.
+  throughput=True: the device draws its own noise and words (noise=None, tape=None) and the oracles draw theirs from
+  the same Philox streams (key=TP_KEY), on a batch that is not a multiple of 64 with envs moved off the trivial counter
+  (_throughput_counters); the same tolerances, budgets and exactness rules apply.
 
   Stated tolerance: after one step from identical fp32 state, qpos/qvel agree within
   1e-4 (abs + rel) with the fp64 oracle and 2e-5 with the fp32 oracle, except for
@@ -282,7 +328,7 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale):
   cost flags are exact except where the oracle reports the decision within 1e-5 of its
   threshold.  Observations are checked as a function of the device's own post-step state (tight) and end to
   end against the oracle's within the bound that the actual state difference implies (_lidar_e2e_bound)."""
-  n, T = 192 * scale, 160
+  n, T = (130, 120) if throughput else (192 * scale, 160)
   rid = {'point': 0, 'car': 1}[robot]
   od = 60 if robot == 'point' else 72
   if task == MIXED:
@@ -295,7 +341,7 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale):
     rf, ri = bu.sample_records(robot, task, n, seed=666)
   if task not in ('haul_box',):
     rf = bu.goal_beyond_box(rf, ri)
-  ctx = nat.Context(robot, n, seed=1234)
+  ctx = nat.Context(robot, n, seed=TP_SEED if throughput else 1234)
   ctx.set_layout(rf, ri)
   rng = np.random.RandomState(7)
   mt = np.random.RandomState(99)
@@ -303,6 +349,9 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale):
   rf, ri = ctx.get_state()
   arr = oracle.make_batch(rf, ri)
   np.testing.assert_allclose(obs0, oracle.observe_batch(arr, rid, od), rtol=0, atol=OBS_TOL)
+  if throughput:
+    _throughput_counters(nat, ctx, n)
+  draws = np.zeros(4, np.int64)
   n_met = n_cost = n_near = viol64 = viol32 = acc_bad = acc_e2e = 0
   bad64_env, bad32_env = np.zeros(n, int), np.zeros(n, int)
   for t in range(T):
@@ -311,9 +360,16 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale):
     act = bu.pursuit_actions(rf, ri, rng, robot=robot)
     noise = mt.normal(size=(n, 2)).astype(np.float32)
     tape = mt.randint(0, 2**32, size=(n, 64), dtype=np.uint32)
-    d_obs, d_rew, d_cost, d_done, d_met, d_used = ctx.step(act, noise, tape)
-    o_obs, o_rew, o_cost, o_done, o_met, o_used, o_margin = oracle.step_batch_full(arr, rid, act, noise, tape, obs_dim=od)
-    o32 = oracle32.step_batch_full(arr32, rid, act, noise, tape, obs_dim=od)
+    key = (0, 0)
+    if throughput:
+      noise = tape = None
+      key = TP_KEY
+    d_obs, d_rew, d_cost, d_done, d_met, d_used = ctx.step(act, noise, tape, want_tape_used=throughput)
+    o_obs, o_rew, o_cost, o_done, o_met, o_used, o_margin = oracle.step_batch_full(arr, rid, act, noise, tape, key=key, obs_dim=od)
+    o32 = oracle32.step_batch_full(arr32, rid, act, noise, tape, key=key, obs_dim=od)
+    if throughput:
+      draws += _draw_counts(nat, ri, o_met, o_used)
+      noise = _oracle_noise(oracle, ri, 2)   # (the accelerometer check below re-evaluates with this step's control)
     d_rf, d_ri = ctx.get_state()
     o_rf, o_ri = oracle.batch_records(arr)
     o32_rf, _ = oracle32.batch_records(arr32)
@@ -368,7 +424,7 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale):
     # accelerometer = forward dynamics at the post-step state incl. stiff contact forces
     # (k = 2770 /s^2 per metre of penetration, b = 105 /s per m/s): checked as a function of
     # the device's own post-step state; end to end it is only counted
-    f_acc = oracle.step_batch_full(oracle.make_batch(d_rf, d_ri), rid, act, noise, tape, nstep=0, obs_dim=od)[0][:, 48:50]
+    f_acc = oracle.step_batch_full(oracle.make_batch(d_rf, d_ri), rid, act, noise, tape, key=key, nstep=0, obs_dim=od)[0][:, 48:50]
     acc_bad += int((np.abs(d_obs[:, 48:50] - f_acc) > 2e-2 + 2e-3 * np.abs(f_acc)).any(1).sum())
     acc_e2e += int((np.abs(d_obs[:, 48:50] - o_obs[:, 48:50]) > 2e-2 + 5e-3 * np.abs(o_obs[:, 48:50])).any(1).sum())
     np.testing.assert_allclose(d_rew[ok], o_rew[ok], rtol=0, atol=2e-4, err_msg=f'reward step {t}')
@@ -406,6 +462,16 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale):
   assert viol32 <= budget, f'{viol32} env-steps outside the fp32 tolerance'
   assert acc_bad <= 0.0005 * n * T, f'{acc_bad} accelerometer readings off on identical state'
   assert acc_e2e <= 0.005 * n * T, f'{acc_e2e} accelerometer readings off end to end'
+  if throughput:
+    _log_lockstep(f'{robot}/{task} throughput mode: in-step draws by the device generator - goal resamples {draws[0]}, CatchGoal '
+                  f'radius redraws {draws[1]}, goal-button choices {draws[2]}, words {draws[3]}')
+    has = lambda *ids: np.isin(ri[:, nat.I_TASK], ids).any()   # noqa: E731
+    if (~np.isin(ri[:, nat.I_TASK], [1, 8, 9])).any():
+      assert draws[0] > 0, 'no goal was resampled'
+    if has(0):
+      assert draws[1] > 0, 'no CatchGoal radius was redrawn'
+    if has(8, 9):
+      assert draws[2] > 0, 'no goal button was chosen'
   ctx.close()
 
 
@@ -1003,6 +1069,18 @@ DOGGO_C4 = 'multitask-4096'   # BASELINE config 4 at one rank's size
 
 @pytest.mark.parametrize('task', DOGGO_TASKS + [DOGGO_C4])
 def test_doggo_lockstep_vs_oracle(nat, oracle, task):
+  _doggo_lockstep(nat, oracle, task)
+
+
+def test_doggo_lockstep_throughput_vs_oracle(nat, oracle):
+  """The Doggo lockstep in throughput mode: its action noise comes from its own code site in the cooperative physics
+  kernel.  70 envs of the multitask mix, counters moved as _throughput_counters does; after landing, the goal of every
+  GoToGoal-family env is put on its robot and the goal button of every PressButtons env under it, so goal resamples and
+  button choices are drawn by the device generator within the run."""
+  _doggo_lockstep(nat, oracle, MIXED, throughput=True)
+
+
+def _doggo_lockstep(nat, oracle, task, throughput=False):
   """Same protocol as test_step_lockstep_vs_oracle for the Doggo robot (BASELINE config 4 shape
   for 'multitask').  Stated tolerance after one step (12 substeps) from identical fp32 state:
   robot qpos within 2e-5, qvel within 2e-3 abs + 2e-3 rel of the fp64 oracle (the device solves the
@@ -1013,7 +1091,7 @@ def test_doggo_lockstep_vs_oracle(nat, oracle, task):
   `multitask-4096` is BASELINE config 4 at its stated size per rank (4096 envs, ~290 per task, 14 steps: VERDICT r3
   item 2), the oracle on every host core.  Cost flags that differ away from any threshold are counted over the WHOLE
   run (round 3 allowed one per step) and budgeted at 2 - 3 x the measured count (profiles/r04_lockstep_counts.txt)."""
-  n, T = (4096, 14) if task == DOGGO_C4 else (64, 30)
+  n, T = (4096, 14) if task == DOGGO_C4 else (70, 30) if throughput else (64, 30)
   from safe_adaptation_gym_amd import benchmark
   if task == DOGGO_C4:
     oracle.lib.sago_set_threads(os.cpu_count() or 1)
@@ -1022,12 +1100,15 @@ def test_doggo_lockstep_vs_oracle(nat, oracle, task):
   else:
     names = task
   rf, ri = bu.sample_records_native('doggo', names, n, seed=666)
-  ctx = nat.Context('doggo', n, seed=4321)
+  ctx = nat.Context('doggo', n, seed=TP_SEED if throughput else 4321)
   ctx.set_layout(rf, ri)
   mt = np.random.RandomState(5)
   obs0 = ctx.observe()
   rf, ri = ctx.get_state()
   np.testing.assert_allclose(obs0, oracle.observe_batch(oracle.make_batch(rf, ri), 2, 104), rtol=0, atol=OBS_TOL)
+  if throughput:
+    _throughput_counters(nat, ctx, n)
+  draws = np.zeros(4, np.int64)
   E = 144
   pos_f = [0, 1, 2, E] + list(range(E + 1, E + 5)) + list(range(E + 9, E + 22))
   viol = n_rows = 0
@@ -1040,8 +1121,22 @@ def test_doggo_lockstep_vs_oracle(nat, oracle, task):
       act[:] = 0   # let the robots land first
     noise = mt.normal(size=(n, 12)).astype(np.float32)
     tape = mt.randint(0, 2**32, size=(n, 64), dtype=np.uint32)
-    d_obs, d_rew, d_cost, d_done, d_met, d_used = ctx.step(act, noise, tape)
-    o_obs, o_rew, o_cost, o_done, o_met, o_used, o_margin = oracle.step_batch_full(arr, 2, act, noise, tape, obs_dim=104)
+    key = (0, 0)
+    if throughput:
+      noise = tape = None
+      key = TP_KEY
+      if t == 4:   # standing: goals onto the robots, goal buttons under them
+        g = np.isin(ri[:, nat.I_TASK], [3, 4, 5, 6])
+        rf[g, nat.F_GOAL:nat.F_GOAL + 2] = rf[g, nat.F_ROBOT:nat.F_ROBOT + 2]
+        for i in np.flatnonzero(np.isin(ri[:, nat.I_TASK], [8, 9])):
+          b = nat.F_BUTTONS + 2 * ri[i, nat.I_GOAL_BUTTON]
+          rf[i, b:b + 2] = rf[i, nat.F_ROBOT:nat.F_ROBOT + 2]
+        ctx.set_state(rf, ri)
+        arr = oracle.make_batch(rf, ri)
+    d_obs, d_rew, d_cost, d_done, d_met, d_used = ctx.step(act, noise, tape, want_tape_used=throughput)
+    o_obs, o_rew, o_cost, o_done, o_met, o_used, o_margin = oracle.step_batch_full(arr, 2, act, noise, tape, key=key, obs_dim=104)
+    if throughput:
+      draws += _draw_counts(nat, ri, o_met, o_used)
     d_rf, d_ri = ctx.get_state()
     o_rf, o_ri = oracle.batch_records(arr)
     tol = np.full(d_rf.shape[1], 2e-3)
@@ -1085,6 +1180,10 @@ def test_doggo_lockstep_vs_oracle(nat, oracle, task):
   assert flag_mism <= flag_budget, f'{flag_mism} cost flags differ away from a threshold'
   if task == DOGGO_C4:
     oracle.lib.sago_set_threads(1)
+  if throughput:
+    _log_lockstep(f'doggo/{task} throughput mode: in-step draws by the device generator - goal resamples {draws[0]}, CatchGoal '
+                  f'radius redraws {draws[1]}, goal-button choices {draws[2]}, words {draws[3]}')
+    assert draws[0] > 0 and draws[1] > 0 and draws[2] > 0, f'draws not exercised: {draws}'
   ctx.close()
 
 
@@ -1546,3 +1645,277 @@ def test_doggo_cooperative_linear_algebra(nat, oracle):
     np.testing.assert_allclose(qacc[k], oqacc, rtol=1e-7, atol=1e-9)
     np.testing.assert_allclose(Minv[k] @ oM, np.eye(19), atol=1e-7)
   ctx.close()
+
+
+# ----------------------------------------------------------------------------------
+# throughput mode: action noise the comparison can see, deep goal resamples, the bench's own loop
+# ----------------------------------------------------------------------------------
+def _state_tol(nat, robot):
+  """The lockstep's per-field state tolerance against the fp64 oracle (abs; the same value again relative)."""
+  if robot == 'doggo':
+    E = 144
+    tol = np.full(nat.REC_FLOATS, 2e-3)
+    tol[[0, 1, 2, E] + list(range(E + 1, E + 5)) + list(range(E + 9, E + 22))] = 2e-5
+    for k in range(10):
+      tol[81 + 6 * k:81 + 6 * k + 6] = STATE_TOL
+      tol[81 + 6 * k + 5] = 2e-4
+    tol[41:47] = STATE_TOL; tol[46] = 5e-3
+    return tol
+  tol = np.full(nat.REC_FLOATS, STATE_TOL)
+  for wf in [46] + [81 + 6 * k + 5 for k in range(10)]:
+    tol[wf] = 2e-4
+  return tol
+
+
+def _rows_off(d_rf, o_rf, tol):
+  return (np.abs(d_rf - o_rf) > tol + tol * np.abs(o_rf)).any(1)
+
+
+@pytest.mark.parametrize('robot', ['point', 'car', 'doggo'])
+def test_throughput_action_noise_vs_oracle(nat, oracle, robot):
+  """One throughput step at action_noise 0.5 (F_CTRL_SCALE widened 4x so the clamp rarely binds): a wrong noise draw now
+  moves the state far beyond the lockstep tolerances, and the step must still match the oracle's throughput step.  The
+  controls show that the comparison sees the noise: the same device step against the oracle with the wrong key1, with the
+  episode nonce off by one, and (the device fed sago_noise_ep's values explicitly) with z0 / z1 of each pair swapped and,
+  for the Doggo, whose noise is drawn at its own code site, shifted by one joint.  Each control must put a quarter of the
+  envs outside the tolerance; the shares and the largest device-versus-oracle difference are logged."""
+  rid, nu, od = {'point': (0, 2, 60), 'car': (1, 2, 72), 'doggo': (2, 12, 104)}[robot]
+  n = 70 if robot == 'doggo' else 130
+  rf, ri = bu.sample_records_native(robot, 'go_to_goal', n, seed=31)
+  rf[:, nat.F_ACTION_NOISE] = 0.5
+  rf[:, nat.F_CTRL_SCALE:nat.F_CTRL_SCALE + nu] *= 4
+  ctx = nat.Context(robot, n, seed=TP_SEED)
+  ctx.set_layout(rf, ri)
+  rf, ri = _throughput_counters(nat, ctx, n)
+  act = np.random.RandomState(8).uniform(-0.3, 0.3, (n, nu)).astype(np.float32)
+  tol = _state_tol(nat, robot)
+
+  def oracle_state(key=TP_KEY, ri_=ri, noise=None):
+    arr = oracle.make_batch(rf, ri_)
+    o = oracle.step_batch_full(arr, rid, act, noise, None, key=key, obs_dim=od)
+    return oracle.batch_records(arr)[0], o
+
+  def device_state(noise=None):
+    ctx.set_state(rf, ri)
+    d = ctx.step(act, noise, None, want_tape_used=True)
+    return ctx.get_state()[0], d
+
+  d_rf, d = device_state()
+  o_rf, o = oracle_state()
+  off = _rows_off(d_rf, o_rf, tol)
+  body = list(range(0, 6)) + (list(range(144, 144 + 38)) if robot == 'doggo' else [])
+  worst = float(np.abs(d_rf[:, body] - o_rf[:, body]).max())
+  moved = float(np.abs(d_rf[:, 3:6]).max())
+  np.testing.assert_array_equal(d[5], o[5])
+  np.testing.assert_allclose(d[1][~off], o[1][~off], rtol=0, atol=2e-4)
+  assert off.sum() <= (0.005 * n if robot == 'doggo' else 0), f'{off.sum()} of {n} envs outside the lockstep tolerance'
+  wrong_ep = ri.copy()
+  wrong_ep[:, nat.I_EPISODE] = (wrong_ep[:, nat.I_EPISODE] + 1) & 0xffffff
+  z = _oracle_noise(oracle, ri, nu)
+  controls = {'wrong key1': oracle_state(key=(TP_KEY[0], TP_KEY[1] ^ 1))[0],
+              'episode nonce + 1': oracle_state(ri_=wrong_ep)[0]}
+  swapped = z.reshape(n, -1, 2)[:, :, ::-1].reshape(n, nu)
+  dev_controls = {'z0 / z1 swapped': device_state(swapped)[0]}
+  if robot == 'doggo':
+    dev_controls['noise shifted by one joint'] = device_state(np.roll(z, 1, axis=1))[0]
+  # (the explicit-noise path with the oracle's own draws reproduces the throughput step: the controls differ in the draw alone)
+  assert not _rows_off(device_state(z)[0], d_rf, tol)[~off].any()
+  shares = {k: float(_rows_off(d_rf, v, tol).mean()) for k, v in controls.items()}
+  shares.update({k: float(_rows_off(v, o_rf, tol).mean()) for k, v in dev_controls.items()})
+  _log_lockstep(f'{robot}: {n} envs, action_noise 0.5, one throughput step | largest |device - oracle| state difference {worst:.3g} '
+             f'(robot velocities reach {moved:.3g}); envs outside the tolerance {int(off.sum())} | controls, share of envs outside: '
+             + ', '.join(f'{k} {v:.3f}' for k, v in shares.items()))
+  for k, v in shares.items():
+    assert v >= 0.25, f'control "{k}" leaves {v:.3f} of the envs inside the tolerance: the comparison does not see the noise'
+  ctx.close()
+
+
+def _philox_np(c, key):
+  """Philox4x32-10 in NumPy (uint64 lanes), for the independent walk of the resample."""
+  M = np.uint64(0xffffffff)
+  c = [np.asarray(x, np.uint64) & M for x in c]
+  k0, k1 = np.uint64(key[0]), np.uint64(key[1])
+  for _ in range(10):
+    p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+    c = [(p1 >> np.uint64(32)) ^ c[1] ^ k0, p1 & M, (p0 >> np.uint64(32)) ^ c[3] ^ k1, p0 & M]
+    k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
+  return c
+
+
+def _goal_walk(env, step, episode, pos0, robot_xy, n_cand, key=TP_KEY):
+  """GoToGoal._resample_goal_position over utils.draw_placement (tasks/go_to_goal.py:59-80, utils.py:51-79, 118-119) in
+  float64: candidate j is drawn in the rectangle +-1.5 grown by 1 % per earlier rejection, shrunk by the goal keepout 0.4,
+  from the four stream-0 words at position pos0 + 4 j.  Returns the candidates' xy and distances to the robot."""
+  w = pos0 + np.arange(4 * n_cand, dtype=np.int64)
+  blk = _philox_np([np.full(len(w), env), np.full(len(w), step), w >> 2, np.full(len(w), episode << 2)], key)
+  words = np.choose((w & 3).astype(int), blk).reshape(n_cand, 4)
+  u = ((words[:, [0, 2]] >> np.uint64(5)).astype(np.float64) * 67108864.0 + (words[:, [1, 3]] >> np.uint64(6))) / 9007199254740992.0
+  half = np.empty(n_cand)
+  h = 1.5
+  for j in range(n_cand):
+    half[j] = h
+    h *= 1.01
+  lo, hi = -half + 0.4, half - 0.4
+  xy = lo[:, None] + (hi - lo)[:, None] * u
+  return xy, np.hypot(xy[:, 0] - robot_xy[0], xy[:, 1] - robot_xy[1])
+
+
+def _keepout_for_depth(dist, target):
+  """A robot keepout whose first accepted candidate is the first record of `dist` at or past `target`: halfway between the
+  farthest earlier candidate and that record (a wide margin either side)."""
+  run = np.maximum.accumulate(dist)
+  J = next(j for j in range(max(target, 1), len(dist)) if dist[j] > run[j - 1])
+  return 0.5 * (run[J - 1] + dist[J]) - 0.4, J
+
+
+def test_throughput_deep_goal_resample(nat, oracle):
+  """The wave-cooperative goal resample past the first wavefront pass.  An empty Point world with the goal on each robot
+  (met in the step); robot keepouts (F_KEEPOUT + 0, read only by the resample) chosen from an independent float64 walk of
+  the reference's candidate sequence so the first accepted candidate falls at j ~ 40 (past what a 64-word tape holds),
+  ~ 70 (second pass), ~ 300 (fifth pass) and, for a CatchGoal env whose 10-step timer expires in the same step (its
+  radius redraw takes words 0 - 1: the resample starts at stream position 2), ~ 70; plus a keepout of +inf that no
+  candidate clears (the 10 000-try failure: flag bit 0, 40 000 words).  Device against the oracle in throughput mode
+  and with 2048-word tapes: new goal xy, I_FLAGS bits 0 / 1 and words consumed, exactly; a 100-word tape that runs out
+  mid-search (flag bit 1, position); and the device's position == 4 (j + 1) of the walk's first accepted j."""
+  from safe_adaptation_gym_amd.tasks.go_to_goal import GoToGoal
+
+  class Empty(GoToGoal):
+    @property
+    def obstacles(self):
+      return [0, 0, 0, 0]
+
+  depths = [0, 40, 70, 300, None, 70]   # None: +inf keepout; the last env is the CatchGoal one
+  n = len(depths)
+  rf, ri, st = nat.sample_layouts('point', 7000 + np.arange(n), 0, descs=[Empty().descriptor()])
+  assert not st.any()
+  rf[:, nat.F_ACTION_NOISE] = 0     # the robot stays at rest: the walk's robot position is the pre-step one
+  rf[:, 3:6] = 0
+  ri[:, nat.I_EPISODE] = [0, 2**23, 1, 0xfffffe, 5, 2]
+  ri[:, nat.I_STEP] = [0, 17, 1000, 3, 9, 40]
+  rf[:, nat.F_GOAL:nat.F_GOAL + 2] = rf[:, nat.F_ROBOT:nat.F_ROBOT + 2]
+  cg = n - 1
+  ri[cg, nat.I_TASK] = 0                       # catch_goal: origin on the robot, radius 0 now, timer expiring
+  ri[cg, nat.I_CATCH_TIMER] = 1
+  rf[cg, nat.F_CATCH:nat.F_CATCH + 2] = rf[cg, nat.F_ROBOT:nat.F_ROBOT + 2]
+  rf[cg, nat.F_CATCH + 2:nat.F_CATCH + 4] = 0
+  want_j = []
+  for i, dep in enumerate(depths):
+    pos0 = 2 if i == cg else 0
+    _, dist = _goal_walk(ri[i, nat.I_ENV_ID], ri[i, nat.I_STEP], ri[i, nat.I_EPISODE], pos0, rf[i, :2], 400)
+    if dep is None:
+      rf[i, nat.F_KEEPOUT] = np.inf
+      want_j.append(None)
+    else:
+      k, J = _keepout_for_depth(dist, dep)
+      rf[i, nat.F_KEEPOUT] = k
+      want_j.append(J)
+  ctx = nat.Context('point', n, seed=TP_SEED)
+  ctx.set_layout(rf, ri)
+  rf, ri = ctx.get_state()     # (the keepouts as the device holds them: fp32)
+  assert np.isinf(rf[4, nat.F_KEEPOUT])
+  act = np.zeros((n, 2), np.float32)
+  lines = []
+  for tape_len in (None, 2048, 100):
+    ctx.set_state(rf, ri)
+    tape = None if tape_len is None else np.random.RandomState(tape_len).randint(0, 2**32, (n, tape_len), dtype=np.uint32)
+    d = ctx.step(act, None, tape, want_tape_used=True)
+    d_rf, d_ri = ctx.get_state()
+    arr = oracle.make_batch(rf, ri)
+    o = oracle.step_batch_full(arr, 0, act, None, tape, key=TP_KEY)
+    o_rf, o_ri = oracle.batch_records(arr)
+    assert d[4].all() and o[4].all(), 'every goal is met in the step'
+    np.testing.assert_array_equal(d[5], o[5], err_msg=f'words consumed, tape {tape_len}')
+    np.testing.assert_array_equal(d_ri[:, nat.I_FLAGS] & 3, o_ri[:, nat.I_FLAGS] & 3, err_msg=f'flags, tape {tape_len}')
+    np.testing.assert_array_equal(d_rf[:, nat.F_GOAL:nat.F_GOAL + 2], o_rf[:, nat.F_GOAL:nat.F_GOAL + 2],
+                                  err_msg=f'new goal, tape {tape_len}')
+    np.testing.assert_allclose(d_rf, o_rf, rtol=STATE_TOL, atol=STATE_TOL)
+    lines.append(f'tape {tape_len}: words {d[5].tolist()}, flags {(d_ri[:, nat.I_FLAGS] & 3).tolist()}')
+    if tape_len is None:
+      for i, J in enumerate(want_j):
+        pos0 = 2 if i == cg else 0
+        if J is None:
+          assert d[5][i] == 40000 and d_ri[i, nat.I_FLAGS] & 3 == 1, 'the 10 000-try failure'
+          continue
+        assert d[5][i] == pos0 + 4 * (J + 1), f'env {i}: device position {d[5][i]}, walk accepts j = {J}'
+        xy, _ = _goal_walk(ri[i, nat.I_ENV_ID], ri[i, nat.I_STEP], ri[i, nat.I_EPISODE], pos0, d_rf[i, :2], J + 1)
+        np.testing.assert_array_equal(d_rf[i, nat.F_GOAL:nat.F_GOAL + 2], xy[J].astype(np.float32))
+      assert not (d_ri[:5, nat.I_FLAGS] & 2).any()
+    elif tape_len == 2048:
+      assert (d_ri[[4], nat.I_FLAGS] & 3 == 2).all(), '+inf keepout on a 2048-word tape: the tape runs out first'
+      assert not (d_ri[[0, 1, 2, 3, 5], nat.I_FLAGS] & 3).any()
+    else:
+      assert d_ri[2, nat.I_FLAGS] & 3 == 2 and d[5][2] == 104, 'a 100-word tape ends in the 26th candidate'
+  _log_lockstep(f'deep resample: first accepted candidate j {want_j} (keepouts {[float(x) for x in rf[:, nat.F_KEEPOUT]]}) | '
+                + ' | '.join(lines))
+  ctx.close()
+
+
+@pytest.mark.parametrize('task', ['go_to_goal', MIXED])
+def test_bench_device_run_vs_oracle(nat, oracle, task):
+  """bench.py's own loop (DeviceRun: k_fill_actions' synthetic policy in N_ACTION_BUFS device buffers, sag_step_device in
+  throughput mode) for 300 envs (not a multiple of 256) and more steps than there are action buffers: after every step
+  its output buffers against the oracle's throughput step from the device's pre-step state, with the policy's actions
+  taken from sago_actions((666, 0), env, t % N_ACTION_BUFS).  The lockstep's rules: observation and reward tolerances,
+  done exact, goal_met exact on rows inside the state tolerance, cost flags exact away from a threshold."""
+  import sys
+  sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+  import bench
+  n, T = 300, bench.N_ACTION_BUFS + 4
+  run = bench.DeviceRun(task, n, 0, 0)
+  tol = _state_tol(nat, 'point')
+  n_met = n_cost = 0
+  for t in range(T):
+    rf, ri = run.ctx.get_state()
+    arr = oracle.make_batch(rf, ri)
+    acts = np.array([oracle.actions((666, 0), int(e), t % bench.N_ACTION_BUFS, 2) for e in ri[:, nat.I_ENV_ID]], np.float32)
+    run.step()
+    d = run.outputs()
+    o_obs, o_rew, o_cost, o_done, o_met, o_used, o_margin = oracle.step_batch_full(arr, 0, acts, key=(666, 0))
+    d_rf, d_ri = run.ctx.get_state()
+    o_rf, o_ri = oracle.batch_records(arr)
+    ok = ~_rows_off(d_rf, o_rf, tol)
+    assert ok.mean() > 0.99, f'step {t}: {int((~ok).sum())} envs outside the state tolerance'
+    np.testing.assert_array_equal(d['done'], o_done)
+    np.testing.assert_array_equal(d['goal_met'][ok], o_met[ok], err_msg=f'goal_met step {t}')
+    np.testing.assert_array_equal(d_ri[ok], o_ri[ok], err_msg=f'task ints step {t}')
+    hard, _ = _flags_agree(d['cost'][ok], o_cost[ok], o_margin[ok])
+    assert hard == 0, f'cost flag mismatch away from any threshold at step {t}'
+    e2e = _lidar_e2e_bound(nat, d_rf, o_rf)
+    worst = np.abs(d['obs'][ok, :48] - o_obs[ok, :48]).max(1) - e2e[ok]
+    assert (worst <= 0).all(), f'lidar e2e step {t}'
+    np.testing.assert_allclose(d['obs'][ok, 50:], o_obs[ok, 50:], rtol=2e-4, atol=2e-4, err_msg=f'sensors step {t}')
+    np.testing.assert_allclose(d['reward'][ok], o_rew[ok], rtol=0, atol=2e-4, err_msg=f'reward step {t}')
+    n_met += int(d['goal_met'].sum()); n_cost += int(d['cost'].sum())
+  print(f'bench DeviceRun {task}: {n} envs x {T} steps, goal-met events {n_met}, cost events {n_cost}')
+  run.close()
+
+
+@pytest.mark.parametrize('robot,nu', [('point', 2), ('doggo', 12)])
+def test_fill_actions_bitexact(nat, oracle, robot, nu):
+  """k_fill_actions (the bench's synthetic policy) against sago_actions, bit for bit: 1, 255 and 257 envs (the tail of its
+  256-thread grid), env ids offset as build_records(rank=1) sets them, step indices 0, 7 and >= 2^31, and the Philox word
+  whose top 24 bits are set (env 233889 at step 2^31 + 5 under TP_KEY), the one that maps to +1."""
+  import sys
+  sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+  import bench
+  for N in (1, 255, 257):
+    rf, ri = bench.build_records('go_to_goal', N, 1, robot=robot)
+    assert ri[0, nat.I_ENV_ID] == N
+    if N == 257:
+      ri[200, nat.I_ENV_ID] = 233889
+    for seed in (666, TP_SEED):
+      key = (seed & 0xffffffff, seed >> 32)
+      ctx = nat.Context(robot, N, seed=seed)
+      ctx.set_layout(rf, ri)
+      buf = ctx.dev_alloc(N * nu * 4)
+      for step in (0, 7, 2**31 + 5, 2**32 - 1):
+        ctx.dev_fill_actions(buf, step)
+        ctx.wait()
+        got = ctx.dev_download(buf, (N, nu), np.float32)
+        want = np.array([oracle.actions(key, int(e), step, nu) for e in ri[:, nat.I_ENV_ID]], np.float32)
+        np.testing.assert_array_equal(got, want, err_msg=f'{N} envs, step {step}')
+        assert (np.abs(got) <= 1).all()
+        if N == 257 and seed == TP_SEED and step == 2**31 + 5:
+          assert got[200, 0] == np.float32(1)
+      ctx.dev_free(buf)
+      ctx.close()
