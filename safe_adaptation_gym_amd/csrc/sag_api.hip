@@ -49,32 +49,19 @@ struct sag_ctx {
   // the quiet kernel (many short memory-bound ones); fork/join events order them against the main stream
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  // Side by side with the busy kernel the quiet kernel requests this much unused LDS on top of its own
-  // 10 KB: a quiet wavefront then frees at least what a busy one needs (13 KB), so a waiting busy
-  // workgroup (higher stream priority) fits into any hole a quiet one leaves.  With 10-KB holes the busy
-  // kernel, which sets the length of a step, is starved of LDS by the far more numerous quiet
-  // workgroups once the batch exceeds what is resident at once (measured at 4 M envs: +8 % throughput,
-  // tools/ab.sh run; SAG_QUIET_LDS_EXTRA overrides, bytes; < 0 = busy kernel's footprint minus the quiet one's).
-  int quiet_lds_extra = -1;
   int early_fork = -1;  // quiet stream forks before the compaction: 1 / 0, -1 = by batch size (SAG_EARLY_FORK)
-  bool overlap = true;  // SAG_OVERLAP=0: both kernels on the main stream, one after the other
   float* S = nullptr;
   int32_t* I = nullptr;
   float* G = nullptr;  // [3][NBODY][N] spill of body accelerations beyond the LDS pool
-  // busy lists (split launches): [2][N] rows and two counters, used alternately by `phase`.  A step
-  // consumes list[phase] and its classification appends list[phase ^ 1]; k_compact rebuilds
-  // list[phase] from the busy bits whenever state was installed from outside (list_valid = false)
+  // busy lists (split launches), rebuilt by k_compact from the busy bits before every busy launch:
+  // rows [BUSY_CLASSES][N]; d_count holds two sets of BUSY_CLASSES counters, used alternately (a
+  // compaction fills one and zeroes the other for the next step), then the env count of the last busy launch
   int32_t* d_rows = nullptr; int32_t* d_count = nullptr;
   uint8_t* d_kind = nullptr;   // [N] kind of every busy env (BUSY_CLASSES)
-  bool list_valid = false;
-  int count_flip = 0;          // which of the counter sets 2 and 3 of d_count this step's compaction fills
+  int count_flip = 0;          // which counter set of d_count this step's compaction fills
   int32_t* last_count = nullptr;
   float* d_hot = nullptr;     // [N][HOT_FLOATS] hot records (split form), see sag_device.hpp
-  bool hot_valid = false, use_hot = true;   // SAG_HOT=0 disables
-  // SAG_INKERNEL_LIST=1: the step kernels append the next busy list themselves and k_compact only runs
-  // after installs.  Measured no faster (0.37 vs 0.35 ms at 1M envs): the 15 us saved are lost to the
-  // worse row locality of chunks in arrival order (k_compact emits rows sorted per 4096-env block).
-  bool inkernel_list = false;
+  bool hot_valid = false;
   // last installed layout (sag_reset)
   float* L_f = nullptr;   // [N][SAG_REC_FLOATS] AoS, device
   int32_t* L_i = nullptr; // [N][SAG_REC_INTS]
@@ -101,9 +88,6 @@ struct sag_ctx {
   double* d_dr = nullptr;    // Doggo: per-env result block of the physics kernel (k_doggo_physics: 2 envs per wavefront)
   int32_t* d_dg_sched = nullptr; int dg_phase = 0;   // Doggo: longest-first launch order (sag_doggo_coop.hpp); SAG_DOGGO_SCHED=0 turns it off
   bool dg_sched_on = true;
-  int epw_override = 0;  // SAG_EPW (read once at create): envs per wavefront of the single-launch form
-  int busy_e = 64;       // SAG_BUSY_E: envs per busy wavefront (0 = balanced over busy_slots: busy_wave_envs - measured slower, see there)
-  int busy_slots = 0;    // SAG_BUSY_SLOTS: busy wavefronts resident at once (0 = 8 per CU: two per SIMD)
   int busy_kinds = -1;   // SAG_BUSY_KINDS: 1 = the busy list by kind of contact, 0 = one list; default: the Car (the Point's step is its quiet kernel: no gain)
   int kinds_min = -1;    // SAG_BUSY_KINDS_MIN: busy envs of the step before above which the kinds are used (default: 64 per resident slot; tests: 0)
   bool split = true;   // QUIET + BUSY launches; SAG_SPLIT=0/1 in the environment forces the form
@@ -284,9 +268,8 @@ int launch_step(sag_ctx* c, const float* d_act, const float* d_noise, const uint
   a.tape_used = d_used; a.max_vases = c->cfg.max_vases; a.max_hazards = c->cfg.max_hazards;
   a.max_pillars = c->cfg.max_pillars; a.max_buttons = c->cfg.max_buttons; a.observe_only = observe_only;
   a.has_box = c->cfg.has_box; a.G = c->G;
-  // busy lists: [phase][BUSY_CLASSES][N] rows; counters [4][BUSY_CLASSES]: two for the in-kernel lists (by phase), two used alternately by k_compact
-  a.phase = c->phase; a.rows = c->d_rows + (size_t)c->phase * BUSY_CLASSES * c->N; a.count = c->d_count + c->phase * BUSY_CLASSES;
-  a.rows_next = nullptr; a.count_next = nullptr; a.DR = nullptr; a.dg_sched = nullptr; a.dg_phase = -1;
+  a.phase = c->phase; a.rows = c->d_rows; a.count = nullptr;   // (the busy list: split form, below)
+  a.DR = nullptr; a.dg_sched = nullptr; a.dg_phase = -1;
   a.hot = nullptr; a.hot_haz = nullptr;
   // external contact results: for the one step with nstep == 0 that follows sag_set_ext_contacts
   const bool use_ext = c->ext_pending && !observe_only && a.nstep == 0;
@@ -294,14 +277,13 @@ int launch_step(sag_ctx* c, const float* d_act, const float* d_noise, const uint
   if (!observe_only) c->ext_pending = false;
   {
     // single-launch form: aim for four wavefronts per CU (Doggo: one - only one fits its LDS working
-    // set), down to 16 (Doggo 8) envs per wavefront (tools/epw_sweep.py: Car 4096 envs 0.58 -> 0.48 ms)
+    // set), down to 16 (Doggo 8) envs per wavefront (measured by a sweep of envs per wavefront: Car 4096 envs 0.58 -> 0.48 ms)
     const bool dg = c->cfg.robot == SAG_ROBOT_DOGGO;
     int epw = 64;
     while (epw > (dg ? 8 : 16) && (c->N + epw - 1) / epw < (dg ? 1 : 4) * c->n_cu) epw >>= 1;
-    if (c->epw_override > 0) epw = c->epw_override;
-    a.envs_per_wave = epw < 1 ? 1 : (epw > 64 ? 64 : epw);
-    a.busy_envs = c->busy_e; a.busy_kinds = c->busy_kinds < 0 ? c->cfg.robot == SAG_ROBOT_CAR : c->busy_kinds; a.kind = a.busy_kinds ? c->d_kind : nullptr; a.busy_total = c->d_count + 4 * BUSY_CLASSES;
-    a.busy_slots = c->busy_slots > 0 ? c->busy_slots : 8 * c->n_cu;
+    a.envs_per_wave = epw;
+    a.busy_kinds = c->busy_kinds < 0 ? c->cfg.robot == SAG_ROBOT_CAR : c->busy_kinds; a.kind = a.busy_kinds ? c->d_kind : nullptr; a.busy_total = c->d_count + 2 * BUSY_CLASSES;
+    a.busy_slots = 8 * c->n_cu;   // two busy wavefronts per SIMD
   }
   c->phase_used = c->phase;
   if (!observe_only) c->phase ^= 1;
@@ -318,24 +300,18 @@ int launch_step(sag_ctx* c, const float* d_act, const float* d_noise, const uint
   const bool split = c->split && !observe_only && c->cfg.robot != SAG_ROBOT_DOGGO;
   hipStream_t quiet_stream = c->stream;
   if (split) {
-    a.rows_next = c->d_rows + (size_t)(c->phase_used ^ 1) * BUSY_CLASSES * c->N; a.count_next = c->d_count + (c->phase_used ^ 1) * BUSY_CLASSES;
-    if (c->use_hot && c->d_hot) {
-      a.hot = c->d_hot; a.hot_haz = c->d_hot + (size_t)c->N * HOT_FLOATS;
-      if (!c->hot_valid) {
-        hipLaunchKernelGGL(k_hot_refresh, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->S, c->I, c->N, c->d_hot, c->d_hot + (size_t)c->N * HOT_FLOATS);
-        c->hot_valid = true;
-      }
+    a.hot = c->d_hot; a.hot_haz = c->d_hot + (size_t)c->N * HOT_FLOATS;
+    if (!c->hot_valid) {
+      hipLaunchKernelGGL(k_hot_refresh, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->S, c->I, c->N, c->d_hot, c->d_hot + (size_t)c->N * HOT_FLOATS);
+      c->hot_valid = true;
     }
-    if (!c->inkernel_list) { a.rows_next = nullptr; a.count_next = nullptr; c->list_valid = false; }
-    else HIPCHK(c, hipMemsetAsync(a.count_next, 0, BUSY_CLASSES * sizeof(int32_t), c->stream));
     // The quiet kernel needs no list (it reads the busy bits), so its stream forks off BEFORE the
     // compaction: k_compact only looks at this step's copy of the bit, which the quiet kernel never
     // changes (it rewrites tstate words of quiet envs with that bit still clear), so the two may overlap.
     // Only when the batch is large enough to keep the chip full (>= SAG_EARLY_FORK_MIN_ENVS): below that a
     // step is as long as its busy wavefronts, which must then be resident first (1 M envs: 15 % slower
     // with the early fork, 4 M envs: 10 % faster; profiles/r01_v16_early_fork_ab.txt).
-    const bool early_fork = c->overlap && !c->inkernel_list &&
-                            (c->early_fork < 0 ? (c->N >= SAG_EARLY_FORK_MIN_ENVS && c->cfg.robot != SAG_ROBOT_CAR) : c->early_fork != 0);
+    const bool early_fork = c->early_fork < 0 ? (c->N >= SAG_EARLY_FORK_MIN_ENVS && c->cfg.robot != SAG_ROBOT_CAR) : c->early_fork != 0;
     // (Car: its busy kernel is 4x longer than the quiet one and sets the step; with the early fork the quiet grid
     // occupies the chip first and the busy wavefronts start late: 3.49 vs 3.15 ms at 4 M envs)
     if (early_fork) {
@@ -343,45 +319,38 @@ int launch_step(sag_ctx* c, const float* d_act, const float* d_noise, const uint
       HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
       quiet_stream = c->stream2;
     }
-    if (!c->inkernel_list) {
-      // two counters used alternately: this step's compaction zeroes the one the next step will use
-      a.count = c->d_count + (2 + c->count_flip) * BUSY_CLASSES;
-      if (a.busy_kinds)
-        hipLaunchKernelGGL(k_compact<true>, dim3((c->N + COMPACT_ENVS - 1) / COMPACT_ENVS), dim3(256), 0, c->stream, c->I, c->d_kind, c->N, a.phase,
-                           a.rows, a.count, c->d_count + (2 + (c->count_flip ^ 1)) * BUSY_CLASSES, a.busy_total, c->kinds_min >= 0 ? c->kinds_min : 64 * a.busy_slots);
-      else
-        hipLaunchKernelGGL(k_compact<false>, dim3((c->N + COMPACT_ENVS - 1) / COMPACT_ENVS), dim3(256), 0, c->stream, c->I, c->d_kind, c->N, a.phase,
-                           a.rows, a.count, c->d_count + (2 + (c->count_flip ^ 1)) * BUSY_CLASSES, a.busy_total, 0);
-      c->count_flip ^= 1;
-    } else if (!c->list_valid) {
-      HIPCHK(c, hipMemsetAsync(a.count, 0, BUSY_CLASSES * sizeof(int32_t), c->stream));
-      if (a.busy_kinds)
-        hipLaunchKernelGGL(k_compact<true>, dim3((c->N + COMPACT_ENVS - 1) / COMPACT_ENVS), dim3(256), 0, c->stream, c->I, c->d_kind, c->N, a.phase,
-                           a.rows, a.count, (int32_t*)nullptr, a.busy_total, c->kinds_min >= 0 ? c->kinds_min : 64 * a.busy_slots);
-      else
-        hipLaunchKernelGGL(k_compact<false>, dim3((c->N + COMPACT_ENVS - 1) / COMPACT_ENVS), dim3(256), 0, c->stream, c->I, c->d_kind, c->N, a.phase,
-                           a.rows, a.count, (int32_t*)nullptr, a.busy_total, 0);
-    }
+    // two counter sets used alternately: this step's compaction zeroes the one the next step will use
+    a.count = c->d_count + c->count_flip * BUSY_CLASSES;
+    int32_t* const zero_for_next = c->d_count + (c->count_flip ^ 1) * BUSY_CLASSES;
+    if (a.busy_kinds)
+      hipLaunchKernelGGL(k_compact<true>, dim3((c->N + COMPACT_ENVS - 1) / COMPACT_ENVS), dim3(256), 0, c->stream, c->I, c->d_kind, c->N, a.phase,
+                         a.rows, a.count, zero_for_next, a.busy_total, c->kinds_min >= 0 ? c->kinds_min : 64 * a.busy_slots);
+    else
+      hipLaunchKernelGGL(k_compact<false>, dim3((c->N + COMPACT_ENVS - 1) / COMPACT_ENVS), dim3(256), 0, c->stream, c->I, c->d_kind, c->N, a.phase,
+                         a.rows, a.count, zero_for_next, a.busy_total, 0);
+    c->count_flip ^= 1;
     c->last_count = a.count;
-    c->list_valid = true;
-    if (c->overlap && !early_fork) {
+    if (!early_fork) {
       HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
       HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
       quiet_stream = c->stream2;
     }
   }
-  // LDS the quiet kernel asks for beyond what it uses (see sag_ctx::quiet_lds_extra)
+  // Side by side with the busy kernel the quiet kernel requests unused LDS on top of its own 10 KB: a quiet
+  // wavefront then frees at least what a busy one needs (13 KB), so a waiting busy workgroup (higher stream
+  // priority) fits into any hole a quiet one leaves.  With 10-KB holes the busy kernel, which sets the length of
+  // a step, is starved of LDS by the far more numerous quiet workgroups once the batch exceeds what is resident
+  // at once (measured at 4 M envs: +8 % throughput, tools/ab.sh run).
   size_t quiet_lds_extra = 0;
-  if (split && c->overlap) {
+  if (split) {
     const int quiet_own = (LS_YAW + (c->cfg.robot == SAG_ROBOT_CAR ? 25 : 17)) * WAVE * (int)sizeof(float);
     const int busy_own = LDS_FLOATS * (int)sizeof(float) + WAVE * (int)sizeof(int);
-    const int want = c->quiet_lds_extra >= 0 ? c->quiet_lds_extra : (busy_own > quiet_own ? (busy_own - quiet_own + 511) / 512 * 512 : 0);
-    quiet_lds_extra = (size_t)want;
+    quiet_lds_extra = busy_own > quiet_own ? (busy_own - quiet_own + 511) / 512 * 512 : 0;
   }
 #define SAG_LAUNCH3(ROB, B_, X_)                                                                         \
   do {                                                                                                  \
     if (split) {                                                                                        \
-      hipLaunchKernelGGL((k_step_busy<ROB, B_, X_>), dim3(busy_grid(c->N, a.busy_envs, a.busy_slots)), dim3(WAVE), 0, c->stream, a); \
+      hipLaunchKernelGGL((k_step_busy<ROB, B_, X_>), dim3(busy_grid(c->N)), dim3(WAVE), 0, c->stream, a); \
       hipLaunchKernelGGL((k_step_quiet<ROB, B_, X_>), dim3(blocks), dim3(WAVE), quiet_lds_extra, quiet_stream, a); \
     } else {                                                                                            \
       hipLaunchKernelGGL((k_step<ROB, B_, X_>), dim3((c->N + a.envs_per_wave - 1) / a.envs_per_wave), dim3(WAVE), 0, c->stream, a); \
@@ -419,7 +388,7 @@ int launch_step(sag_ctx* c, const float* d_act, const float* d_noise, const uint
   }
 #undef SAG_LAUNCH
 #undef SAG_LAUNCH3
-  if (split && c->overlap) {
+  if (split) {
     HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
   }
@@ -521,14 +490,7 @@ int sag_create(const sag_config* cfg, sag_ctx** out) {
   }
   CREATE_CHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   CREATE_CHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-  if (const char* e = getenv("SAG_OVERLAP")) c->overlap = atoi(e) != 0;
   if (const char* e = getenv("SAG_EARLY_FORK")) c->early_fork = atoi(e);
-  if (const char* e = getenv("SAG_QUIET_LDS_EXTRA")) c->quiet_lds_extra = atoi(e) > 65536 ? 65536 : atoi(e);
-  if (const char* e = getenv("SAG_INKERNEL_LIST")) c->inkernel_list = atoi(e) != 0;
-  if (const char* e = getenv("SAG_HOT")) c->use_hot = atoi(e) != 0;
-  if (const char* e = getenv("SAG_EPW")) c->epw_override = atoi(e);
-  if (const char* e = getenv("SAG_BUSY_E")) c->busy_e = atoi(e) > 64 ? 64 : atoi(e);
-  if (const char* e = getenv("SAG_BUSY_SLOTS")) c->busy_slots = atoi(e);
   if (const char* e = getenv("SAG_BUSY_KINDS")) c->busy_kinds = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("SAG_BUSY_KINDS_MIN")) c->kinds_min = atoi(e);
   {
@@ -538,11 +500,11 @@ int sag_create(const sag_config* cfg, sag_ctx** out) {
   CREATE_CHK(hipMalloc(&c->S, N * DEV_FLOATS * sizeof(float)));
   CREATE_CHK(hipMalloc(&c->I, icount(N) * sizeof(int32_t)));
   CREATE_CHK(hipMalloc(&c->G, N * 3 * NBODY * sizeof(float)));
-  CREATE_CHK(hipMalloc(&c->d_rows, 2 * BUSY_CLASSES * N * sizeof(int32_t)));
+  CREATE_CHK(hipMalloc(&c->d_rows, BUSY_CLASSES * N * sizeof(int32_t)));
   CREATE_CHK(hipMalloc(&c->d_kind, N));
   CREATE_CHK(hipMemset(c->d_kind, 0, N));
-  CREATE_CHK(hipMalloc(&c->d_count, (4 * BUSY_CLASSES + 1) * sizeof(int32_t)));   // (+ the env count of the last busy launch)
-  CREATE_CHK(hipMemset(c->d_count, 0, (4 * BUSY_CLASSES + 1) * sizeof(int32_t)));
+  CREATE_CHK(hipMalloc(&c->d_count, (2 * BUSY_CLASSES + 1) * sizeof(int32_t)));   // (+ the env count of the last busy launch)
+  CREATE_CHK(hipMemset(c->d_count, 0, (2 * BUSY_CLASSES + 1) * sizeof(int32_t)));
   CREATE_CHK(hipMalloc(&c->L_f, N * SAG_REC_FLOATS * sizeof(float)));
   CREATE_CHK(hipMalloc(&c->L_i, N * SAG_REC_INTS * sizeof(int32_t)));
   CREATE_CHK(hipMalloc(&c->st_f, N * SAG_REC_FLOATS * sizeof(float)));
@@ -556,7 +518,7 @@ int sag_create(const sag_config* cfg, sag_ctx** out) {
   CREATE_CHK(hipMalloc(&c->d_done, N));
   CREATE_CHK(hipMalloc(&c->d_met, N));
   CREATE_CHK(hipMalloc(&c->d_used, N * sizeof(int32_t)));
-  if (c->split && c->use_hot && cfg->robot != SAG_ROBOT_DOGGO)
+  if (c->split && cfg->robot != SAG_ROBOT_DOGGO)
     CREATE_CHK(hipMalloc(&c->d_hot, N * (HOT_FLOATS + 20) * sizeof(float)));
   if (cfg->robot == SAG_ROBOT_DOGGO) {
     CREATE_CHK(hipMalloc(&c->d_dr, N * DR_STRIDE * sizeof(double)));
@@ -635,7 +597,7 @@ int sag_set_layout(sag_ctx* c, const int32_t* env_ids, int32_t n, const float* r
   if (rc) return rc;
   hipLaunchKernelGGL(k_install, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->S, c->I, c->N,
                      env_ids ? c->st_ids : nullptr, n, c->st_f, c->st_i, 1);
-  c->list_valid = false; c->hot_valid = false;  // busy bits / state changed outside a step
+  c->hot_valid = false;  // state changed outside a step
   c->ext_pending = false;   // contact results supplied for another state do not carry over (sag_set_ext_contacts: "for the NEXT step")
   hipLaunchKernelGGL(k_clear_cost, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_cost, env_ids ? c->st_ids : nullptr, n);
   // keep a copy for sag_reset: read the installed state back into the AoS layout store
@@ -663,7 +625,7 @@ int sag_set_state(sag_ctx* c, const int32_t* env_ids, int32_t n, const float* re
   if (rc) return rc;
   hipLaunchKernelGGL(k_install, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->S, c->I, c->N,
                      env_ids ? c->st_ids : nullptr, n, c->st_f, c->st_i, 0);
-  c->list_valid = false; c->hot_valid = false;  // busy bits / state changed outside a step
+  c->hot_valid = false;  // state changed outside a step
   c->ext_pending = false;
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -711,7 +673,7 @@ int sag_reset(sag_ctx* c, const int32_t* env_ids, int32_t n) {
                        c->st_ids, n, c->st_f, c->st_i, 0);
   }
   hipLaunchKernelGGL(k_clear_cost, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_cost, env_ids ? c->st_ids : nullptr, n);
-  c->list_valid = false; c->hot_valid = false;  // busy bits / state changed outside a step
+  c->hot_valid = false;  // state changed outside a step
   c->ext_pending = false;
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -114,8 +114,7 @@ struct CarFricK {
 struct StepArgs {
   CarFricK car;
   int envs_per_wave;  // single-launch form (k_step): 8..64 envs per wavefront, by batch size
-  int busy_envs;      // split form (k_step_busy): envs per busy wavefront, or 0 = balanced over `busy_slots` (busy_wave_envs)
-  int busy_slots;     // busy wavefronts the chip holds at once
+  int busy_slots;     // busy wavefronts the chip holds at once (sets the default threshold of the busy kinds)
   int busy_kinds;     // 1: the busy list is kept by kind (BUSY_CLASSES); 0: one list (SAG_BUSY_KINDS=0, A/B)
   uint8_t* kind;      // [N] kind of every busy env, for the next step's compaction
   int32_t* busy_total;  // the busy launch leaves its env count here
@@ -141,8 +140,6 @@ struct StepArgs {
   int32_t phase;          // which copy of the busy bit this launch reads (0 / 1)
   int32_t* rows;          // [BUSY_CLASSES][N] env ids of the busy envs by kind, compacted (k_compact)
   int32_t* count;         // [BUSY_CLASSES] entries in each list
-  int32_t* rows_next;     // split form: the busy list of the NEXT step, appended to by the classification
-  int32_t* count_next;    //   (nullptr: not built; the host then runs k_compact)
   float* G;               // [3][NBODY][N] spill of body accelerations beyond the LDS pool
   int32_t observe_only;   // 1: sag_observe (no noise/physics/reward/cost)
   const int32_t* ext_cc;  // sag_set_ext_contacts: [N] contact counts (>= 0: replaces the geometric result) or nullptr
@@ -318,9 +315,6 @@ __device__ inline float impedance(float depth) {
 __device__ inline void solve_contact(BV& A, BV& B, float nx, float ny, float px, float py,
                                      float depth, const Sol& sol) {
 #pragma clang fp contract(on)   // a * b + c of ONE expression fuses (frontend decision: the same in every instance)
-#if defined(SAG_ABL_CL) && SAG_ABL_CL == 4   // timing-only: pair and vertex tests without the contact solve
-  return;
-#endif
   float rax = px - A.x, ray = py - A.y, rbx = px - B.x, rby = py - B.y;
   float vx, vy, ax, ay, ua[3] = {0, 0, 0}, ub[3] = {0, 0, 0};
   rel_at(A, B, rax, ray, rbx, rby, vx, vy, ax, ay);
@@ -445,7 +439,6 @@ __device__ inline int bb_contact(BV& A, BV& B, float ax, float ay, float ca, flo
 // the gap along an axis exceeds 1e-5 m; bb_contact's vertices must be strictly inside).  Most pairs that pass the
 // bounding circles are thin bumpers beside a box: 40 instructions here instead of 2 x 4 vertex transforms there.
 constexpr float SAT_EPS = 1e-5f;
-#ifndef SAG_NO_SAT
 __device__ inline bool boxes_separated(float ax, float ay, float ca, float sa, float ahx, float ahy, float bx, float by,
                                        float cb, float sb, float bhx, float bhy) {
 #pragma clang fp contract(on)   // a * b + c of ONE expression fuses (frontend decision: the same in every instance)
@@ -456,9 +449,6 @@ __device__ inline bool boxes_separated(float ax, float ay, float ca, float sa, f
   return fabsf(ta_x) > ahx + bhx * c + bhy * s + SAT_EPS || fabsf(ta_y) > ahy + bhx * s + bhy * c + SAT_EPS ||
          fabsf(tb_x) > bhx + ahx * c + ahy * s + SAT_EPS || fabsf(tb_y) > bhy + ahx * s + ahy * c + SAT_EPS;
 }
-#else   // (diagnosis: results must be bit-identical with and without the cull - tests/diag_traj.py)
-__device__ inline bool boxes_separated(float, float, float, float, float, float, float, float, float, float, float, float) { return false; }
-#endif
 
 __device__ inline double dist2d(double ax, double ay, double bx, double by) {
   double dx = ax - bx, dy = ay - by;
@@ -572,9 +562,6 @@ __device__ inline int collide_list_nb(BV& A, float ca, float sa, BV& B, int shB,
 #pragma clang fp contract(on)   // a * b + c of ONE expression fuses (frontend decision: the same in every instance)
   constexpr int NA = SHA == SH_ROBOT ? 2 : (SHA == SH_CAR ? 8 : 1);
   static_assert(SHA == SH_ROBOT || SHA == SH_CAR || SHA == SH_VASE, "shapes with a compile-time geom list");
-#if defined(SAG_ABL_CL) && SAG_ABL_CL == 2   // timing-only: no pair test at all
-  return 0;
-#endif
   const float rc = ca * cb + sa * sb, rs = sa * cb - ca * sb;   // x axis of A . x axis of B, x axis of A . y axis of B
   const float ac = fabsf(rc), as = fabsf(rs);
   // B's geoms: centre in A's frame (relative to A's origin), half extents projected on A's axes
@@ -593,11 +580,8 @@ __device__ inline int collide_list_nb(BV& A, float ca, float sa, BV& B, int shB,
   const float obx = cb * odx + sb * ody, oby = cb * ody - sb * odx;
   typedef typename std::conditional<(NA > 4), uint64_t, uint32_t>::type mask_t;
   mask_t mask = 0;   // bit 8 ga + gb
-#ifndef SAG_CL_UNROLL_A
-#define SAG_CL_UNROLL_A 8
-#endif
   // (the car's 8 x 5 pairs fully unrolled keep 15 + temporaries alive and spill: its geom loop stays rolled)
-  constexpr int UNROLL_A = NA * NB > SAG_CL_UNROLL_A ? 1 : NA;
+  constexpr int UNROLL_A = NA * NB > 8 ? 1 : NA;
 #pragma unroll UNROLL_A
   for (int ga = 0; ga < NA; ga++) {
     const Geom a = shape_geom(SHA, ga, vsz, rstatic);
@@ -615,9 +599,6 @@ __device__ inline int collide_list_nb(BV& A, float ca, float sa, BV& B, int shB,
     }
   }
   int n = 0;
-#if defined(SAG_ABL_CL) && SAG_ABL_CL == 1   // timing-only: the bounding-circle pass alone
-  mask = 0;
-#endif
   while (mask) {
     const int pbit = (NA > 4 ? __ffsll((unsigned long long)mask) : __ffs((unsigned int)mask)) - 1;
     mask &= mask - 1;
@@ -669,22 +650,12 @@ constexpr int LDS_FLOATS = LDS_SLOTS * WAVE;
 // once or twice in it - the friction solve's warm-start forces and its share of the base acceleration, the spin
 // accelerations, the rear ball's quaternion - are parked in [slot][lane] LDS slots behind the body slots instead of
 // holding registers the pair walk needs (that instance spilled 73 VGPRs = 256 B of scratch per lane, and 2048 resident
-// wavefronts x 64 x 256 B is more than the chip's L2: the spills went to HBM).  SAG_CAR_PARK=0: in registers (A/B).
-#ifndef SAG_CAR_PARK
-#define SAG_CAR_PARK 1
-#endif
-constexpr int CAR_PARK_SLOTS = SAG_CAR_PARK ? 23 : 0;
+// wavefronts x 64 x 256 B is more than the chip's L2: the spills went to HBM).
+constexpr int CAR_PARK_SLOTS = 23;
 enum { CP_FL = 0, CP_F0 = 5, CP_PX = 8, CP_EACC = 11, CP_Q = 16, CP_TAIL = 20 };
 #define CPK(j) lds[(LDS_SLOTS + (j)) * WAVE + lane]
 constexpr int STG_BASE = LS_YAW * WAVE;
 
-// timing-only ablations (tools/ablate.py): -DSAG_ABLATE=<mask>; results are wrong by design
-#ifndef SAG_ABLATE
-#define SAG_ABLATE 0
-#endif
-enum { ABL_NO_LIDAR = 1, ABL_NO_OBS_STORE = 2, ABL_NO_VV = 4, ABL_NO_VS = 8, ABL_NO_RV = 16, ABL_NO_RS = 32,
-       ABL_NSUB1 = 64, ABL_NO_ACTIVE = 128, ABL_NO_RESAMPLE = 8192 };
-#define ABL(f) ((SAG_ABLATE & (f)) != 0)
 // section profile (tools/cycles.py): -DSAG_CYCLES accumulates wavefront clock ticks per code
 // section of step_body into g_cyc[mode][section]; off in the shipped library
 enum { CY_LOAD = 0, CY_ROBOT, CY_RS, CY_RV, CY_VS, CY_VV_BROAD, CY_VV_NARROW, CY_INTEG, CY_WRITEBACK,
@@ -743,10 +714,7 @@ namespace sag {
 #define STG(j) lds[STG_BASE + lane * STG_STRIDE + (j)]  // STG_STRIDE: constexpr of the enclosing kernel
 // The 16 lidar bins of a chunk accumulate in a [bin][lane] tile over the same region (the bank is the lane: the
 // data-dependent bin of an atomic never conflicts; the [lane][17] rows did - SQ_LDS_BANK_CONFLICT was 1.4 x
-// SQ_ACTIVE_INST_LDS in k_step_quiet<0>, round 3).  SAG_LIDAR_TILE=0: the row layout (A/B).
-#ifndef SAG_LIDAR_TILE
-#define SAG_LIDAR_TILE 1
-#endif
+// SQ_ACTIVE_INST_LDS in k_step_quiet<0>, round 3).
 #define TILE(b) lds[STG_BASE + (b) * WAVE + lane]
 
 // tstate bits 17..27: body k has non-zero velocity or may overlap something (derived at
@@ -847,7 +815,6 @@ __device__ inline float angle_bins(float ex, float ey) {
   return t;
 }
 
-template <int STG_STRIDE>
 __device__ inline void lidar_point(float* lds, int lane, float rxf, float ryf, float yawf, float cf, float sf,
                                    float px, float py) {
   const float w0 = px - rxf, w1 = py - ryf;
@@ -871,24 +838,14 @@ __device__ inline void lidar_point(float* lds, int lane, float rxf, float ryf, f
   const int bp = (bin + 1) & 15, bm = (bin + 15) & 15;
   // closeness values are >= +0, so their bit patterns order like the floats: LDS integer
   // atomic max (ds_max_i32, no return value) replaces read-max-write and its round trips
-#if SAG_LIDAR_TILE
   int* o = reinterpret_cast<int*>(&TILE(0));
   atomicMax(o + bin * WAVE, __float_as_int(sensor));
   atomicMax(o + bp * WAVE, __float_as_int(alias * sensor));
   atomicMax(o + bm * WAVE, __float_as_int((1.0f - alias) * sensor));
-#else
-  int* o = reinterpret_cast<int*>(&STG(0));
-  atomicMax(o + bin, __float_as_int(sensor));
-  atomicMax(o + bp, __float_as_int(alias * sensor));
-  atomicMax(o + bm, __float_as_int((1.0f - alias) * sensor));
-#endif
 }
 
 #ifndef SAG_STEP_MIN_WAVES
 #define SAG_STEP_MIN_WAVES 2  // 245 VGPRs: 8 waves per CU; forcing 3 per SIMD spills (measured slower)
-#endif
-#ifndef SAG_LDS_PAD
-#define SAG_LDS_PAD 0
 #endif
 // HAS_BTN / HAS_TBOX: compile-time knowledge that the context holds no buttons / no task object
 // (capacities of sag_create); the specialised instances drop those arrays, loops and the box
@@ -901,7 +858,6 @@ __device__ inline void lidar_point(float* lds, int lane, float rxf, float ryf, f
 //  BUSY   the envs whose bit is set, compacted (k_compact) into full wavefronts, full physics.  QUIET + BUSY together do exactly what ALL does (tests compare them).
 // Doggo lidar: the base is tilted, so e = (d @ R)[:2] with d = [p_xy, 0] - robot_xpos
 // (safe_adaptation_gym.py:197-216) has a -z R[2,:2] term; evaluated in fp64 as the reference does
-template <int STG_STRIDE>
 __device__ inline void lidar_point_tilted(float* lds, int lane, const double* pos, const double* Rm, float px, float py) {
   const double dx = (double)px - pos[0], dy = (double)py - pos[1], dz = -pos[2];
   const double EX = Rm[0] * dx + Rm[3] * dy + Rm[6] * dz;
@@ -915,17 +871,10 @@ __device__ inline void lidar_point_tilted(float* lds, int lane, const double* po
   const double Dd = hypot(EX, EY);
   const float sensor = (float)((5.0 - Dd > 0 ? 5.0 - Dd : 0.0) / 5.0);
   const int bp = (bin + 1) & 15, bm = (bin + 15) & 15;
-#if SAG_LIDAR_TILE
   int* o = reinterpret_cast<int*>(&TILE(0));
   atomicMax(o + bin * WAVE, __float_as_int(sensor));
   atomicMax(o + bp * WAVE, __float_as_int(alias * sensor));
   atomicMax(o + bm * WAVE, __float_as_int((1.0f - alias) * sensor));
-#else
-  int* o = reinterpret_cast<int*>(&STG(0));
-  atomicMax(o + bin, __float_as_int(sensor));
-  atomicMax(o + bp, __float_as_int(alias * sensor));
-  atomicMax(o + bm, __float_as_int((1.0f - alias) * sensor));
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -1038,7 +987,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
   static_assert(!DOGGO || MODE == MODE_ALL || MODE == MODE_POST, "Doggo runs the single-launch form");
   static_assert(DOGGO || MODE != MODE_POST, "MODE_POST is the Doggo post kernel");
   constexpr bool QUIET = MODE == MODE_QUIET;
-  constexpr bool PARK = CAR && !QUIET && CAR_PARK_SLOTS > 0;   // (CPK slots above)
+  constexpr bool PARK = CAR && !QUIET;   // (CPK slots above)
   constexpr int SH_ME = CAR ? SH_CAR : SH_ROBOT;
   constexpr int OBS_DIM = DOGGO ? 104 : (CAR ? 72 : 60);
   // sensor columns per staged chunk: Doggo's 56 go out as two chunks of 28
@@ -1261,7 +1210,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
   // ---- physics: nstep x (forward, integrate) + one forward at the final state ---
   // padding lanes (they mirror another env so that loads stay in bounds) run no physics at all: they
   // would widen the divergence union and, when the dynamic pool overflows, race on that env's state
-  const int nsub = !live ? -1 : (p.observe_only ? 0 : (ABL(ABL_NSUB1) ? 1 : p.nstep));
+  const int nsub = !live ? -1 : (p.observe_only ? 0 : p.nstep);
   // statics occupy [0, capP) and [SAG_MAX_PILLARS, SAG_MAX_PILLARS + capB) of stx/sty
   const int n_static = capB ? SAG_MAX_PILLARS + capB : capP;
   const uint32_t fmask = ((1u << nV) - 1) | (has_box ? 1u << BOX_ID : 0u);
@@ -1367,9 +1316,6 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     float fL, fT, fR, fX, fY;
     if constexpr (PARK) { fL = CPK(CP_FL); fT = CPK(CP_FL + 1); fR = CPK(CP_FL + 2); fX = CPK(CP_FL + 3); fY = CPK(CP_FL + 4); }
     else { fL = car_fL; fT = car_fT; fR = car_fR; fX = car_fX; fY = car_fY; }
-#ifdef SAG_ABL_CARFRIC   // timing-only build: no floor friction at all
-    car_warm = true;
-#endif
     if (!car_warm) {   // (uniform: the first solve of the step)
       const float b0 = CM * a0 + AB * a2 + p.car.w_T * rT + p.car.w_X * cX;
       const float b1 = CM * a1 + p.car.w_L * cL + p.car.w_L * cR + p.car.w_Y * cY;
@@ -1379,11 +1325,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       fR = clampf(p.car.w_L * (cR - (n1 + 0.13f * n2)), -LIML, LIML); fX = clampf(p.car.w_X * (cX - (n0 + 0.1f * n2)), -LIMC, LIMC);
       fY = clampf(p.car.w_Y * (cY - n1), -LIMC, LIMC);
     }
-#ifdef SAG_ABL_CARFRIC
-    const int nsweeps = 0;
-#else
     const int nsweeps = car_warm ? CAR_FRICTION_SWEEPS_WARM : CAR_FRICTION_SWEEPS;
-#endif
     float g0 = UL0 * fL + UT0 * fT - UL0 * fR + UX0 * fX, g1 = M3 * fL + M3 * fR + M3 * fY, g2 = UL2 * fL + UT2 * fT - UL2 * fR + UX2 * fX;
     float sL = qL + CRW * fL * p.car.iIw, sR = qR + CRW * fR * p.car.iIw, sX = qX + CRW * fX * p.car.iIb, sY = qY + CRW * fY * p.car.iIb;
 #pragma unroll 1
@@ -1484,9 +1426,6 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
         R.m0 = (CM * CIO - b * b) * id; R.m1 = (a * b) * id; R.m2 = (-a * CM) * id;
         R.m3 = (CM * CIO - a * a) * id; R.m4 = (-b * CM) * id; R.m5 = (CM * CM) * id;
       }
-#ifdef SAG_CYC_SPLIT   // (diagnosis: what precedes the friction solve is booked under `load`)
-      CYC(CY_LOAD);
-#endif
       if (sub == nsub) car_warm = false;      // the forward evaluation behind the observation solves cold: obs = f(state)
       car_floor(0.f, R.w * R.w * COY, 0.f);   // M^-1 (centrifugal force of the offset COM) in body axes
       if constexpr (PARK) { CPK(CP_PX) = R.ax; CPK(CP_PX + 1) = R.ay; CPK(CP_PX + 2) = R.aw; }
@@ -1505,7 +1444,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     for (int k = 0; k < n_static; k++) {
       if (k == capP) k = SAG_MAX_PILLARS;  // jump over unused pillar slots to the buttons
       const bool is_p = k < SAG_MAX_PILLARS;
-      const bool on = (is_p ? (k < nP) : (k - SAG_MAX_PILLARS < nB)) && !ABL(ABL_NO_RS);
+      const bool on = (is_p ? (k < nP) : (k - SAG_MAX_PILLARS < nB));
       const float sx = pick(stx, k), syy = pick(sty, k), sr = is_p ? psz : BUTTON_R;
       const float dx = sx - R.x, dyy = syy - R.y, rs = my_bound + sr;
       if (on && dx * dx + dyy * dyy <= rs * rs) {
@@ -1531,7 +1470,6 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       const float dx = LP(LS_X, BOX_ID) - R.x, dyy = LP(LS_Y, BOX_ID) - R.y, rs = my_bound + box_r;
       if (dx * dx + dyy * dyy <= rs * rs) hits |= 1u << BOX_ID;
     }
-    if (ABL(ABL_NO_RV)) hits = 0;
     // (the task object is every lane's LAST hit - BOX_ID is the highest body index - but at different positions of
     // the lanes' lists: walked in one loop, every iteration ran both the 1-geom and the 5-geom form of the pair tests
     // for some lane.  Vases first for all lanes, then the object in one step of its own: the same order per lane.)
@@ -1573,9 +1511,6 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
         }
       }
     }
-#ifdef SAG_CYC_SPLIT   // (diagnosis: the robot's contacts are booked under `robot-static`, the re-solve alone under `robot-free`)
-    CYC(CY_RS);
-#endif
     if constexpr (CAR) {
       // the floor friction once more when the contacts (or the tether) changed the base acceleration: what they
       // added now belongs to `everything else`
@@ -1592,7 +1527,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     if (sub == nsub) for (int k_ = 0; k_ < 6; k_++) { WTT(k_, wt_work[k_] - wt_prev[k_]); wt_prev[k_] = wt_work[k_]; }
 #endif
     if (sub == nsub) break;  // final forward: robot acceleration + contact flags only
-    if (active && !ABL(ABL_NO_ACTIVE)) {
+    if (active) {
       // free bodies vs static circles (pillars then buttons), per active body
       for (uint32_t m = active; m; m &= m - 1) {
         const int k = __ffs(m) - 1;
@@ -1603,7 +1538,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
         for (int q = 0; q < n_static; q++) {
           if (q == capP) q = SAG_MAX_PILLARS;
           const bool is_p = q < SAG_MAX_PILLARS;
-          const bool on = (is_p ? (q < nP) : (q - SAG_MAX_PILLARS < nB)) && !ABL(ABL_NO_VS);
+          const bool on = (is_p ? (q < nP) : (q - SAG_MAX_PILLARS < nB));
           const float dx = pick(stx, q) - bx_, dyy = pick(sty, q) - by_, rs = br + (is_p ? psz : BUTTON_R);
           if (on && dx * dx + dyy * dyy <= rs * rs) shit |= 1u << q;
         }
@@ -1630,23 +1565,21 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       // in ascending order = the specification's pair order.  A body that only becomes active inside
       // this loop was asleep: by the specification its other pairs with sleeping bodies stay skipped.
       uint64_t pairs = 0;
-      if (!ABL(ABL_NO_VV)) {
-        for (uint32_t m = active; m; m &= m - 1) {
-          const int k = __ffs(m) - 1;
-          const float kx = LP(LS_X, k), ky = LP(LS_Y, k), kr = is_box(k) ? box_r : vase_r;
-          // (all positions first, then the tests without branches: read one by one under the hit branch of the body before,
-          // every test waited out an LDS round trip - 2 k cycles per active body, the largest item of a small batch's slowest wavefront)
-          constexpr int NJ = HAS_TBOX ? NBODY : SAG_MAX_VASES;
-          float jx[NJ], jy[NJ];
+      for (uint32_t m = active; m; m &= m - 1) {
+        const int k = __ffs(m) - 1;
+        const float kx = LP(LS_X, k), ky = LP(LS_Y, k), kr = is_box(k) ? box_r : vase_r;
+        // (all positions first, then the tests without branches: read one by one under the hit branch of the body before,
+        // every test waited out an LDS round trip - 2 k cycles per active body, the largest item of a small batch's slowest wavefront)
+        constexpr int NJ = HAS_TBOX ? NBODY : SAG_MAX_VASES;
+        float jx[NJ], jy[NJ];
 #pragma unroll
-          for (int j = 0; j < NJ; j++) { jx[j] = LP(LS_X, j); jy[j] = LP(LS_Y, j); }
+        for (int j = 0; j < NJ; j++) { jx[j] = LP(LS_X, j); jy[j] = LP(LS_Y, j); }
 #pragma unroll
-          for (int j = 0; j < NJ; j++) {
-            const float dx = jx[j] - kx, dyy = jy[j] - ky, rs = kr + (j == BOX_ID ? box_r : vase_r);
-            const bool hit = (fmask >> j & 1u) & (uint32_t)(j != k) & (uint32_t)(dx * dx + dyy * dyy <= rs * rs);
-            const int lo = min(j, k), hi = max(j, k);
-            pairs |= hit ? 1ull << (lo * (21 - lo) / 2 + hi - lo - 1) : 0ull;
-          }
+        for (int j = 0; j < NJ; j++) {
+          const float dx = jx[j] - kx, dyy = jy[j] - ky, rs = kr + (j == BOX_ID ? box_r : vase_r);
+          const bool hit = (fmask >> j & 1u) & (uint32_t)(j != k) & (uint32_t)(dx * dx + dyy * dyy <= rs * rs);
+          const int lo = min(j, k), hi = max(j, k);
+          pairs |= hit ? 1ull << (lo * (21 - lo) / 2 + hi - lo - 1) : 0ull;
         }
       }
       CYC(CY_VV_BROAD);
@@ -1858,20 +1791,6 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     tstate = busy ? (tstate | nbit) : (tstate & ~nbit);
     if (busy && live && p.kind) p.kind[i] = (uint8_t)kind;
     busy_next = busy;
-    // next step's busy list, built here instead of by a separate compaction pass: one atomic per
-    // wavefront claims a contiguous chunk (a chunk keeps the env neighbourhood of its wavefront)
-    if (MODE != MODE_ALL && p.rows_next) {
-      for (int c = 0; c < BUSY_CLASSES; c++) {   // (per kind: the list is [BUSY_CLASSES][N], k_compact)
-        const bool mine = busy && live && (int)kind == c;
-        const uint64_t bm = __ballot(mine);
-        if (bm) {
-          int chunk = 0;
-          if (lane == __ffsll((unsigned long long)bm) - 1) chunk = atomicAdd(p.count_next + c, __popcll(bm));
-          chunk = __shfl(chunk, __ffsll((unsigned long long)bm) - 1);
-          if (mine) p.rows_next[(size_t)c * p.N + chunk + __popcll(bm & ((1ull << lane) - 1))] = i;
-        }
-      }
-    }
   }
 
   CYC(CY_WRITEBACK);
@@ -1997,7 +1916,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
   {
     // (only lanes that carry an env: the padding lanes of a small batch all mirror env N - 1 and would each repeat ITS resample -
     // 48 of them at 16 envs per wavefront, a 0.2-ms spike in every wavefront of the step in which that one env meets its goal)
-    uint64_t need_mask = __ballot(need_goal && live && !ABL(ABL_NO_RESAMPLE));
+    uint64_t need_mask = __ballot(need_goal && live);
     while (need_mask) {
       const int src = __ffsll((unsigned long long)need_mask) - 1;
       need_mask &= need_mask - 1;
@@ -2168,8 +2087,8 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     static_assert(OBS_DIM % 4 == 0 && NSENS % 4 == 0, "observation rows and chunks are whole float4s");
     auto row_of = [&](int e) { return (size_t)(MODE == MODE_BUSY ? rows[e] : base_env + e); };
     auto lid = [&](float px, float py) {
-      if constexpr (DOGGO) lidar_point_tilted<STG_STRIDE>(lds, lane, dgs.pos, dg_rot, px, py);
-      else lidar_point<STG_STRIDE>(lds, lane, R.x, R.y, yaw, cf, sf, px, py);
+      if constexpr (DOGGO) lidar_point_tilted(lds, lane, dgs.pos, dg_rot, px, py);
+      else lidar_point(lds, lane, R.x, R.y, yaw, cf, sf, px, py);
     };
     // Doggo sensors (doggo.xml:83-126 via safe_adaptation_gym.py:225-237): accelerometer, velocimeter,
     // gyro, magnetometer, 8 touch, 12 joint rates, 12 x (sin, cos)
@@ -2196,15 +2115,9 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     for (int chunk = 0; chunk < NCHUNK; chunk++) {
       if (chunk < 3) {
 #pragma unroll
-        for (int k = 0; k < 16; k++) {
-#if SAG_LIDAR_TILE
-          TILE(k) = 0.0f;
-#else
-          STG(k) = 0.0f;
-#endif
-        }
+        for (int k = 0; k < 16; k++) TILE(k) = 0.0f;
       }
-      if (chunk == 0 && !ABL(ABL_NO_LIDAR)) {
+      if (chunk == 0) {
 #pragma unroll 1
         for (int k = 0; k < SAG_MAX_HAZARDS; k++)
           if (k < nH) lid(hzx[k], hzy[k]);
@@ -2265,21 +2178,21 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
                                                                                                     : (int)(((uint32_t)e * 9363u) >> 16)));
           const int c4 = e - env * nq;   // e / nq exact for e < 64 nq (nq = 3, 4, 6, 7)
           float4 v;
-          if (SAG_LIDAR_TILE && chunk < 3) {   // [bin][lane] tile: the env's four bins of this quarter are WAVE floats apart
+          if (chunk < 3) {   // [bin][lane] tile: the env's four bins of this quarter are WAVE floats apart
             const float* t = lds + STG_BASE + (4 * c4) * WAVE + env;
             v = make_float4(t[0], t[WAVE], t[2 * WAVE], t[3 * WAVE]);
           } else {
             const float* t = lds + STG_BASE + env * STG_STRIDE + 4 * c4;
             v = make_float4(t[0], t[1], t[2], t[3]);
           }
-          if (row_ok(env) && !ABL(ABL_NO_OBS_STORE)) o4[row_of(env) * Q + q0 + c4] = v;
+          if (row_ok(env)) o4[row_of(env) * Q + q0 + c4] = v;
         }
       } else if (chunk < 3) {
 #pragma unroll 4
         for (int j = 0; j < 16; j++) {
           const int e = j * WAVE + lane, env = e >> 4, col = e & 15;
-          const float v = SAG_LIDAR_TILE ? lds[STG_BASE + col * WAVE + env] : lds[STG_BASE + env * STG_STRIDE + col];
-          if (row_ok(env) && !ABL(ABL_NO_OBS_STORE)) o[row_of(env) * OBS_DIM + chunk * 16 + col] = v;
+          const float v = lds[STG_BASE + col * WAVE + env];
+          if (row_ok(env)) o[row_of(env) * OBS_DIM + chunk * 16 + col] = v;
         }
       } else {
 #pragma unroll 4
@@ -2290,7 +2203,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
                                       : (int)(((uint32_t)e * 43691u) >> (NSENS == 12 ? 19 : 20));
           const int col = e - env * NSENS;
           const float v = lds[STG_BASE + env * STG_STRIDE + col];
-          if (row_ok(env) && !ABL(ABL_NO_OBS_STORE)) o[row_of(env) * OBS_DIM + 48 + (chunk - 3) * NSENS + col] = v;
+          if (row_ok(env)) o[row_of(env) * OBS_DIM + 48 + (chunk - 3) * NSENS + col] = v;
         }
       }
       __syncthreads();
@@ -2322,7 +2235,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
 // ---- the three launch forms ------------------------------------------------------------
 template <int ROBOT, bool HAS_BTN, bool HAS_TBOX>
 __global__ __launch_bounds__(WAVE, SAG_STEP_MIN_WAVES) void k_step(StepArgs p) {
-  __shared__ float lds[LDS_FLOATS + (ROBOT == SAG_ROBOT_CAR ? CAR_PARK_SLOTS * WAVE : 0) + SAG_LDS_PAD];  // PAD: occupancy probe (tools/ablate.py)
+  __shared__ float lds[LDS_FLOATS + (ROBOT == SAG_ROBOT_CAR ? CAR_PARK_SLOTS * WAVE : 0)];
   static_assert(ROBOT != SAG_ROBOT_DOGGO, "Doggo: k_doggo_physics + k_step_doggo_post");
   // small batches: fewer envs per wavefront (p.envs_per_wave)
   // spread the batch over more CUs and shrink the divergence union; the idle lanes just mirror env N-1
@@ -2356,10 +2269,7 @@ __global__ __launch_bounds__(WAVE, ROBOT == SAG_ROBOT_CAR ? SAG_CAR_QUIET_MIN_WA
   // 10 KB (Point) -> 16 wavefronts per CU
   constexpr int QSLOTS = LS_YAW + (ROBOT == SAG_ROBOT_CAR ? 25 : 17);
   static_assert(QSLOTS >= LS_YAW + NBODY, "the yaw rows written at load time must stay in bounds");
-#ifndef SAG_QUIET_LDS_PAD
-#define SAG_QUIET_LDS_PAD 0
-#endif
-  __shared__ float lds[QSLOTS * WAVE + SAG_QUIET_LDS_PAD];  // PAD: occupancy probe
+  __shared__ float lds[QSLOTS * WAVE];
   const int lane = threadIdx.x, base = blockIdx.x * WAVE, gi = base + lane;
   const bool in = gi < p.N;
   const bool busy = in && ((uint32_t)p.I[iaddr(DI_TSTATE, (size_t)p.N, (size_t)gi)] & (TS_BUSY_BIT << p.phase));
@@ -2387,7 +2297,7 @@ __global__ __launch_bounds__(256) void k_compact(const int32_t* I, const uint8_t
   constexpr int NC = KINDS ? BUSY_CLASSES : 1;
   const bool use_kinds = KINDS && *prev_total > kinds_min;
   // the counters the NEXT step's compaction will add to (saves a memset launch per step)
-  if (zero_for_next && blockIdx.x == 0 && threadIdx.x < BUSY_CLASSES) zero_for_next[threadIdx.x] = 0;
+  if (blockIdx.x == 0 && threadIdx.x < BUSY_CLASSES) zero_for_next[threadIdx.x] = 0;
   __shared__ int wave_tot[4][BUSY_CLASSES];
   __shared__ int wave_base[4][BUSY_CLASSES];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -2437,31 +2347,13 @@ __global__ __launch_bounds__(256) void k_compact(const int32_t* I, const uint8_t
   }
 }
 
-#ifndef SAG_BUSY_PRIO
-#define SAG_BUSY_PRIO 0
-#endif
-// Envs per busy wavefront: 64 (StepArgs::busy_envs).  The alternative below - SAG_BUSY_E=0 - was built on the observation that a
-// launch of W busy wavefronts on `slots` resident ones takes ceil(W / slots) rounds and the last, part-filled round costs a whole
-// one (Car, 4 M envs, one busy list: 6300 wavefronts on ~1900 slots = 3.3 rounds took 1.83 ms where work / slots is 1.33 ms;
-// tools/busy_timeline.py): give every wavefront FEWER envs, just enough to fill the rounds that 64 per wavefront would need anyway.
-// Measured slower for every choice (56 / 48 / 40 envs per wavefront: 2.12 / 2.25 / 2.45 ms against 1.96; profiles/
-// r04_busy_envs_per_wavefront.txt): a busy wavefront's duration does not depend on how many envs it holds - some lane takes every
-// loop either way - so fewer envs per wavefront is simply more wavefronts.  What shortens a wavefront is holding envs of ONE kind
-// (BUSY_CLASSES).  Kept as a switch for measurements.
-constexpr int BUSY_MIN_ENVS = 32;
-__host__ __device__ inline int busy_wave_envs(int count, int slots) {
-  const long long full = 64LL * slots;
-  const long long rounds = (count + full - 1) / full;
-  const long long cap = rounds * slots;   // wavefronts of those rounds
-  const int e = cap > 0 ? (int)((count + cap - 1) / cap) : 64;
-  return e < BUSY_MIN_ENVS ? BUSY_MIN_ENVS : (e > 64 ? 64 : e);
-}
-// blocks a launch must provide for any busy count <= N
-inline int busy_grid(int N, int fixed, int slots) {
-  if (fixed > 0) return (N + fixed - 1) / fixed + BUSY_CLASSES;   // (one part-filled wavefront per kind)
-  const long long a = ((long long)N + BUSY_MIN_ENVS - 1) / BUSY_MIN_ENVS, b = ((long long)N + 63) / 64 + slots;
-  return (int)(a < b ? a : b) + BUSY_CLASSES;
-}
+// Envs per busy wavefront: a full wavefront of 64.  Fewer (just enough to fill the rounds of resident wavefronts that 64 per
+// wavefront would need anyway) was measured slower for every choice (Car, 4 M envs, 56 / 48 / 40 envs per wavefront: 2.12 / 2.25 /
+// 2.45 ms against 1.96; profiles/r04_busy_envs_per_wavefront.txt): a busy wavefront's duration does not depend on how many envs it
+// holds - some lane takes every loop either way - so fewer envs per wavefront is simply more wavefronts.  What shortens a wavefront
+// is holding envs of ONE kind (BUSY_CLASSES).
+// blocks a launch must provide for any busy count <= N (one part-filled wavefront per kind)
+inline int busy_grid(int N) { return (N + WAVE - 1) / WAVE + BUSY_CLASSES; }
 #ifndef SAG_CAR_BUSY_MIN_WAVES
 #define SAG_CAR_BUSY_MIN_WAVES SAG_STEP_MIN_WAVES
 #endif
@@ -2470,30 +2362,21 @@ __global__ __launch_bounds__(WAVE, ROBOT == SAG_ROBOT_CAR ? SAG_CAR_BUSY_MIN_WAV
 #ifdef SAG_WAVE_TIMES
   const unsigned long long wt0 = wall_clock64();
 #endif
-#ifndef SAG_BUSY_LDS_PAD
-#define SAG_BUSY_LDS_PAD 0
-#endif
-  __shared__ float lds[LDS_FLOATS + (ROBOT == SAG_ROBOT_CAR ? CAR_PARK_SLOTS * WAVE : 0) + SAG_BUSY_LDS_PAD];  // PAD: occupancy probe
+  __shared__ float lds[LDS_FLOATS + (ROBOT == SAG_ROBOT_CAR ? CAR_PARK_SLOTS * WAVE : 0)];
   __shared__ int rows[WAVE];
-#if SAG_BUSY_PRIO
-  // the few long wavefronts of this kernel set the length of a step: they issue ahead of the quiet
-  // kernel's wavefronts that share their SIMDs
-  __builtin_amdgcn_s_setprio(SAG_BUSY_PRIO);
-#endif
   // the lists of the kinds one after the other, the expensive kinds first (busy_class_order); a kind's last wavefront may be part-filled
   int b = blockIdx.x, cls = -1, count = 0, total = 0;
 #pragma unroll
   for (int k = 0; k < BUSY_CLASSES; k++) total += p.count[k];
-  const int BE = p.busy_envs > 0 ? p.busy_envs : busy_wave_envs(total, p.busy_slots);
   if (blockIdx.x == 0 && threadIdx.x == 0) *p.busy_total = total;   // (for the next step's k_compact)
 #pragma unroll
   for (int k = 0; k < BUSY_CLASSES; k++) {
-    const int c = busy_class_order(k), n = p.count[c], w = (n + BE - 1) / BE;
+    const int c = busy_class_order(k), n = p.count[c], w = (n + WAVE - 1) / WAVE;
     if (cls < 0) { if (b < w) { cls = c; count = n; } else b -= w; }
   }
   if (cls < 0) return;
-  const int lane = threadIdx.x, c0 = b * BE;
-  const int nval = min(BE, count - c0);
+  const int lane = threadIdx.x, c0 = b * WAVE;
+  const int nval = min(WAVE, count - c0);
   const bool live = lane < nval;
   const int i = p.rows[(size_t)cls * p.N + c0 + (live ? lane : 0)];
   rows[lane] = i;

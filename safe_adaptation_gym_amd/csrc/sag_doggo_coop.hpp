@@ -590,7 +590,7 @@ __device__ __attribute__((noinline)) double dc_rows_finish(int hf, int u, int nr
 }
 
 // a value the optimiser must treat as new at this point (no instruction is emitted)
-#ifndef DC_OPAQUE
+#ifndef DC_OPAQUE   // (the host emulator, tests/hostemu, defines its own form of this hook and of DC_HALF_SELECT)
 #define DC_OPAQUE(x) asm volatile("" : "+v"(x))
 #endif
 // lower half of the wavefront: a, upper half: b.  The lane mask is a CONSTANT (0xffffffff00000000) - written as a
@@ -973,10 +973,7 @@ __device__ __attribute__((noinline)) void dc_pgs_fast(const int hf, const int u,
 // DC_NCLS lists of N env ids.  The order inside a list is the order of arrival: it changes from run to run, the results
 // do not - an env's arithmetic depends on its own row count only (which PGS path it takes is decided per env).
 constexpr int DC_NCLS = 4;
-#ifndef SAG_DC_CLS2
-#define SAG_DC_CLS2 26   // rows from which an env is filed in class 2 / class 1
-#define SAG_DC_CLS1 20
-#endif
+constexpr int DC_CLS2_ROWS = 26, DC_CLS1_ROWS = 20;   // rows from which an env is filed in class 2 / class 1
 __host__ __device__ inline size_t dc_sched_ints(size_t N) { return 16 + 2 * DC_NCLS * N; }
 __host__ __device__ inline int dc_sched_blocks(int N) { return (N + DC_EPW - 1) / DC_EPW; }
 
@@ -1436,7 +1433,7 @@ __global__ __launch_bounds__(32 * DC_EPW) void k_doggo_physics(StepArgs p, doubl
 
   // ---- results: per-env block for the post kernel, state back to HBM ---------------------------
   if (sched && live && u == 0) {   // file the env under its cost class for the next step's order
-    const int cls = rows_max > SAG_DC_FAST_ROWS ? 3 : (rows_max > SAG_DC_CLS2 ? 2 : (rows_max > SAG_DC_CLS1 ? 1 : 0));
+    const int cls = rows_max > SAG_DC_FAST_ROWS ? 3 : (rows_max > DC_CLS2_ROWS ? 2 : (rows_max > DC_CLS1_ROWS ? 1 : 0));
     const int slot = atomicAdd(&sc[((p.dg_phase + 1) % 3) * DC_NCLS + cls], 1);
     sc[16 + ((size_t)((p.dg_phase + 1) & 1) * DC_NCLS + cls) * N + slot] = (int32_t)gi;
   }

@@ -7,7 +7,7 @@
 #   tools/ab.sh pmc   <variant> ...                 instruction counters of the step kernel matching $KEY (default quiet)
 #
 # A <variant> is "" / "default" (libsag.so), the <name> of a built library, or a string of environment
-# assignments ("SAG_EARLY_FORK=0 SAG_HOT=1").  Run-to-run spread on one box is a few %, box to box more:
+# assignments ("SAG_EARLY_FORK=0 SAG_BUSY_KINDS=0").  Run-to-run spread on one box is a few %, box to box more:
 # compare interleaved, in ONE gpurun call.  BENCH_ARGS adds bench.py flags (e.g. "--envs 1048576").
 set -e
 cd "$(dirname "$0")/.."
