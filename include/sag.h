@@ -359,6 +359,35 @@ int sag_sample_layouts_desc(int32_t robot, int32_t n, const uint32_t* seeds, con
                             float* rec_f, int32_t* rec_i, uint32_t* mt_key, int32_t* mt_pos,
                             int32_t* mt_has_gauss, double* mt_gauss, int32_t* status, int32_t nthreads);
 
+/* ---- device reset path (throughput mode) -----------------------------------------------------
+ * The same steps as sag_sample_layouts_desc (placements in the reference's dict order, keep-outs max(keepout, size),
+ * margin + 0.165 for the Doggo, <= 1000 candidates per placement and 10 000 layout attempts, the draws after the layout,
+ * the goal resample, task.reset) sampled on the device, with the words of the counter-based generator (context key,
+ * stream 3) instead of the reference's MT19937: the layouts follow the host sampler's distribution, not its stream.
+ * Parity mode keeps sag_sample_layouts.
+ *
+ * sag_set_tasks: the descriptor table (each checked with sag_task_desc_check and against the context's capacities),
+ * env i's descriptor desc_of_env[i] ([n_envs], host) and the world config, kept on the device.  env_id0 is the global id
+ * of the context's env 0 (SAG_I_ENV_ID, the generator's env word).  Call it when the task set changes. */
+int sag_set_tasks(sag_ctx* ctx, const sag_task_desc* descs, int32_t n_descs, const int32_t* desc_of_env,
+                  const sag_world_config* cfg, int32_t env_id0);
+/* sag_reset_device: samples and installs new layouts on the context stream, without host records.
+ *   first_episode != 0: new Task objects (Cauchy ctrl scale, random bound, fresh button state, catch radii 1 / .2 and timer);
+ *                 0: SAG_F_CTRL_SCALE, SAG_F_BOUND, SAG_I_BTN_STATE, SAG_I_CATCH_TIMER and SAG_F_CATCH + 2, + 3 are kept
+ *                 from the env's current state (needs an installed layout)
+ *   episode0      the episode nonce of envs of a context that has no layout yet; otherwise each reset env's nonce
+ *                 advances by one (as sag_reset), so an env never draws the same layout twice under one key
+ *   d_mask        [n_envs] DEVICE bytes: only envs with a non-zero byte are reset; NULL: every env.  A mask written on
+ *                 another stream must be complete before the call.
+ *   status        [n_envs] host, may be NULL: 0, -1 (layout attempts exhausted), -2 (goal resample exhausted); 0 for envs
+ *                 not reset
+ *   bound         [n_envs] host, may be NULL: every env's SAG_F_BOUND after the call (info['bound'])
+ * Installation is sag_set_layout's (task.reset's `last` distances, overlap flags, cleared cost flag), and the layout store
+ * of sag_reset holds the device-drawn records.  Returns the number of envs whose sampling failed - then NOTHING is
+ * installed - or a negative sag_status.  Synchronous. */
+int sag_reset_device(sag_ctx* ctx, int32_t first_episode, int32_t episode0, const uint8_t* d_mask, int32_t* status,
+                     float* bound);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 
 `make()` mirrors the reference factory (safe_adaptation_gym/__init__.py:6-24) with
 an extra `n_envs` (batch size), `devices` (GPU ordinals to shard over) and `device_buffers` (step() / reset() return
-views of HBM instead of NumPy copies: envs.BatchedSafeAdaptationGym.step)."""
+views of HBM instead of NumPy copies: envs.BatchedSafeAdaptationGym.step) and `device_reset` (reset() samples the layouts on
+the device, throughput mode only, and accepts a mask of envs to reset: envs.BatchedSafeAdaptationGym.reset)."""
 from typing import Dict, Optional
 
 
@@ -16,7 +17,8 @@ def make(robot_name: str,
          n_envs: int = 1,
          devices=None,
          parity_rng: bool = False,
-         device_buffers: bool = False):
+         device_buffers: bool = False,
+         device_reset: bool = False):
   from safe_adaptation_gym_amd.benchmark import ROBOTS_BASENAMES, TASKS
   from safe_adaptation_gym_amd.envs import BatchedSafeAdaptationGym
   env = BatchedSafeAdaptationGym(
@@ -27,6 +29,7 @@ def make(robot_name: str,
       devices=devices,
       parity_rng=parity_rng,
       device_buffers=device_buffers,
+      device_reset=device_reset,
       render_lidars_and_collision=render_lidar_and_collision,
       render_options=render_options)
   env.seed(seed)

@@ -32,7 +32,8 @@ EXPORTS = [
     'sag_reset', 'sag_get_state', 'sag_set_state', 'sag_step', 'sag_step_device', 'sag_wait',
     'sag_observe', 'sag_set_ext_contacts', 'sag_lidar_cost', 'sag_lidar_cost_device', 'sag_set_seed', 'sag_dev_alloc', 'sag_dev_free', 'sag_dev_upload',
     'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_debug_doggo_coop',
-    'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check'
+    'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
+    'sag_set_tasks', 'sag_reset_device'
 ]
 
 
@@ -105,6 +106,8 @@ def load():
   lib.sag_world_config_default.restype = None
   lib.sag_sample_layouts.argtypes = [C.c_int32, C.c_int32, up, ip, C.POINTER(WorldConfig), C.c_int32,
                                      C.c_int32, fp, ip, up, ip, ip, C.POINTER(C.c_double), ip, C.c_int32]
+  lib.sag_set_tasks.argtypes = [vp, vp, C.c_int32, ip, C.POINTER(WorldConfig), C.c_int32]
+  lib.sag_reset_device.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, fp]
   _lib = lib
   return lib
 
@@ -172,14 +175,7 @@ def sample_layouts(robot, seeds, task_ids, config=None, first_episode=True, env_
   seeds = np.ascontiguousarray(np.asarray(seeds, np.int64) % 2**32, np.uint32)
   n = len(seeds)
   tids = np.ascontiguousarray(np.broadcast_to(np.asarray(task_ids, np.int32), (n,)))
-  cfg = WorldConfig()
-  lib.sag_world_config_default(C.byref(cfg))
-  for k, v in (config or {}).items():
-    if k in ('gremlins_size', 'gremlins_keepout', 'gremlins_travel', 'obstacles_size_noise_scale'):
-      continue  # accepted by the reference, without effect (no task spawns gremlins)
-    if not hasattr(cfg, k):
-      raise KeyError(f'unknown world config key {k!r}')
-    setattr(cfg, k, int(v) if k == 'random_bound' else float(v))
+  cfg = world_config(config)
   rf = np.zeros((n, REC_FLOATS), np.float32)
   ri = np.zeros((n, REC_INTS), np.int32)
   status = np.zeros(n, np.int32)
@@ -207,6 +203,20 @@ def sample_layouts(robot, seeds, task_ids, config=None, first_episode=True, env_
     states = [('MT19937', key[j], int(pos[j]), int(hg[j]), float(g[j])) for j in range(n)]
     return rf, ri, status, states
   return rf, ri, status
+
+
+def world_config(config=None):
+  """sag_world_config from World.DEFAULT with the keys of `config` (a dict) applied."""
+  lib = load()
+  cfg = WorldConfig()
+  lib.sag_world_config_default(C.byref(cfg))
+  for k, v in (config or {}).items():
+    if k in ('gremlins_size', 'gremlins_keepout', 'gremlins_travel', 'obstacles_size_noise_scale'):
+      continue  # accepted by the reference, without effect (no task spawns gremlins)
+    if not hasattr(cfg, k):
+      raise KeyError(f'unknown world config key {k!r}')
+    setattr(cfg, k, int(v) if k == 'random_bound' else float(v))
+  return cfg
 
 
 def device_count():
@@ -241,11 +251,12 @@ class DeviceArray:
     return np.lib.stride_tricks.as_strided(full.reshape(-1)[off:], self.shape, self.strides).copy()
 
 
-def device_pointer(x, shape=None, device=None):
+def device_pointer(x, shape=None, device=None, dtype='<f4'):
   """Device pointer of a DeviceArray or of anything that exports __cuda_array_interface__ (a torch / cupy array on the GPU).
   With `shape`, the array is what a step reads as its actions: float32 ('<f4'), exactly that shape, contiguous and - where
   the array says which device it lives on - on `device`.  Anything else raises ValueError before a kernel can read it
-  (a float64 tensor would be read as float32 pairs, a short one past its end)."""
+  (a float64 tensor would be read as float32 pairs, a short one past its end).  `dtype`: the element type required
+  instead of float32 (uint8 for a reset mask)."""
   if isinstance(x, DeviceArray):
     typestr, xshape, strides, ptr = x.dtype.str, x.shape, x.strides, x.ptr
     where = getattr(x.ctx, 'device', None)
@@ -259,8 +270,9 @@ def device_pointer(x, shape=None, device=None):
   if strides is not None and tuple(strides) != tuple(np.zeros(xshape, np.dtype(typestr)).strides):
     raise ValueError('device actions must be contiguous')
   if shape is not None:
-    if np.dtype(typestr) != np.dtype('<f4'):
-      raise ValueError(f'device actions must be float32 (<f4), not {typestr}')
+    if np.dtype(typestr) != np.dtype(dtype):
+      raise ValueError(f'device actions must be float32 (<f4), not {typestr}' if np.dtype(dtype) == np.dtype('<f4') else
+                       f'device array must be {np.dtype(dtype).str}, not {typestr}')
     if tuple(xshape) != tuple(shape):
       raise ValueError(f'device actions of shape {tuple(xshape)}: this shard steps {tuple(shape)}')
     if device is not None and isinstance(where, int) and where != device:
@@ -398,6 +410,30 @@ class Context:
     """The same kernel on device buffers, asynchronous on the context stream (bench: kernel-only time)."""
     self._check(self.lib.sag_lidar_cost_device(self.h, n, K, d_robot, d_points, d_group, hazard_size, d_lidar, d_bins,
                                                d_cost), 'sag_lidar_cost_device')
+
+  def set_tasks(self, descs, desc_of_env, config=None, env_id0=0):
+    """Task descriptors (Task.descriptor() dicts), env i's descriptor index and the world config for sag_reset_device;
+    env_id0 = the global id of this context's env 0."""
+    for k, d in enumerate(descs):
+      msg = task_desc_check(d)
+      if msg:
+        raise SagError(f'task descriptor {k}: {msg}')
+    arr = (TaskDesc * len(descs))(*[TaskDesc.from_dict(d) for d in descs])
+    doe = np.ascontiguousarray(np.broadcast_to(np.asarray(desc_of_env, np.int32), (self.n_envs,)))
+    cfg = world_config(config)
+    self._check(self.lib.sag_set_tasks(self.h, arr, len(descs), _ptr(doe, C.c_int32), C.byref(cfg), int(env_id0)),
+                'sag_set_tasks')
+
+  def reset_device(self, first_episode=False, episode0=0, d_mask=None, want_status=True, want_bound=True):
+    """New layouts sampled and installed on the device (sag_reset_device).  d_mask: device pointer of [n_envs] bytes, or
+    None for every env.  -> (number of envs that failed, status [n_envs] i32 or None, bound [n_envs] f32 or None)."""
+    status = np.zeros(self.n_envs, np.int32) if want_status else None
+    bound = np.zeros(self.n_envs, np.float32) if want_bound else None
+    rc = self.lib.sag_reset_device(self.h, int(bool(first_episode)), int(episode0), d_mask, _ptr(status, C.c_int32),
+                                   _ptr(bound, C.c_float))
+    if rc < 0:
+      self._check(rc, 'sag_reset_device')
+    return rc, status, bound
 
   def set_seed(self, seed):
     """Key of the device-side generator of throughput mode (env.seed())."""

@@ -13,11 +13,13 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "sag_device.hpp"
+#include "sag_reset.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -91,6 +93,14 @@ struct sag_ctx {
   int busy_kinds = -1;   // SAG_BUSY_KINDS: 1 = the busy list by kind of contact, 0 = one list; default: the Car (the Point's step is its quiet kernel: no gain)
   int kinds_min = -1;    // SAG_BUSY_KINDS_MIN: busy envs of the step before above which the kinds are used (default: 64 per resident slot; tests: 0)
   bool split = true;   // QUIET + BUSY launches; SAG_SPLIT=0/1 in the environment forces the form
+  // device reset (sag_set_tasks / sag_reset_device): descriptor table, descriptor of every env, world config
+  sag_task_desc* d_descs = nullptr; int n_descs = 0;
+  int32_t* d_desc_of_env = nullptr;
+  sag_world_config rcfg{};
+  int32_t env_id0 = 0;
+  bool have_tasks = false;
+  int32_t* d_rstat = nullptr;   // [N] status by env, then 2 counters (listed envs, failures)
+  float* d_rbound = nullptr;    // [N]
   std::string err;
 };
 
@@ -548,7 +558,7 @@ int sag_destroy(sag_ctx* c) {
   for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   void* bufs[] = {c->S, c->I, c->G, c->d_rows, c->d_count, c->d_kind, c->L_f, c->L_i, c->st_f, c->st_i, c->st_ids, c->d_act, c->d_noise,
                   c->d_tape, c->d_obs, c->d_rew, c->d_cost, c->d_done, c->d_met, c->d_used, c->scratch, c->d_rgb, c->d_dr, c->d_dg_sched, c->d_hot,
-                  c->d_ext_cc, c->d_ext_btn};
+                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
@@ -678,6 +688,103 @@ int sag_reset(sag_ctx* c, const int32_t* env_ids, int32_t n) {
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SAG_OK;
+}
+
+int sag_set_tasks(sag_ctx* c, const sag_task_desc* descs, int32_t n_descs, const int32_t* desc_of_env, const sag_world_config* cfg,
+                  int32_t env_id0) {
+  if (!c) return SAG_ERR_ARG;
+  if (!descs || n_descs <= 0 || !desc_of_env || !cfg || env_id0 < 0) return fail(c, SAG_ERR_ARG, "sag_set_tasks: bad arguments");
+  for (int k = 0; k < n_descs; k++) {
+    const sag_task_desc& d = descs[k];
+    if (const char* why = sag_task_desc_check(&d)) return fail(c, SAG_ERR_ARG, "task descriptor %d: %s", k, why);
+    if (d.n_hazards > c->cfg.max_hazards || d.n_vases > c->cfg.max_vases || d.n_pillars > c->cfg.max_pillars ||
+        d.n_buttons > c->cfg.max_buttons || (d.box_kind != SAG_BOX_NONE && !c->cfg.has_box))
+      return fail(c, SAG_ERR_ARG, "task descriptor %d exceeds the context's capacities", k);
+  }
+  for (int i = 0; i < c->N; i++)
+    if (desc_of_env[i] < 0 || desc_of_env[i] >= n_descs) return fail(c, SAG_ERR_ARG, "env %d: descriptor %d of %d", i, desc_of_env[i], n_descs);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (n_descs > c->n_descs) {
+    if (c->d_descs) HIPCHK(c, hipFree(c->d_descs));
+    c->d_descs = nullptr; c->n_descs = 0;
+    HIPCHK(c, hipMalloc(&c->d_descs, (size_t)n_descs * sizeof(sag_task_desc)));
+    c->n_descs = n_descs;
+  }
+  if (!c->d_desc_of_env) HIPCHK(c, hipMalloc(&c->d_desc_of_env, (size_t)c->N * sizeof(int32_t)));
+  if (!c->d_rstat) HIPCHK(c, hipMalloc(&c->d_rstat, ((size_t)c->N + 2) * sizeof(int32_t)));
+  if (!c->d_rbound) HIPCHK(c, hipMalloc(&c->d_rbound, (size_t)c->N * sizeof(float)));
+  HIPCHK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n_descs * sizeof(sag_task_desc), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->d_desc_of_env, desc_of_env, (size_t)c->N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));   // the host arrays are the caller's
+  c->rcfg = *cfg; c->env_id0 = env_id0;
+  c->have_tasks = true;
+  return SAG_OK;
+}
+
+int sag_reset_device(sag_ctx* c, int32_t first_episode, int32_t episode0, const uint8_t* d_mask, int32_t* status, float* bound) {
+  if (!c) return SAG_ERR_ARG;
+  if (!c->have_tasks) return fail(c, SAG_ERR_STATE, "sag_reset_device before sag_set_tasks");
+  if (!first_episode && !c->have_layout) return fail(c, SAG_ERR_STATE, "sag_reset_device: a later episode needs an installed layout");
+  if (episode0 < 0 || episode0 > 0xffffff) return fail(c, SAG_ERR_ARG, "episode0 %d is not a 24-bit nonce", episode0);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int N = c->N;
+  int32_t* counters = c->d_rstat + N;   // [0] listed envs, [1] failures
+  HIPCHK(c, hipMemsetAsync(c->d_rstat, 0, ((size_t)N + 2) * sizeof(int32_t), c->stream));
+  int n = N;
+  const int32_t* ids = nullptr;
+  if (d_mask) {
+    hipLaunchKernelGGL(k_reset_list, dim3((N + 255) / 256), dim3(256), 0, c->stream, d_mask, N, c->st_ids, counters);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&n, counters, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    ids = c->st_ids;
+  }
+  int32_t n_fail = 0;
+  if (n > 0) {
+    ResetArgs a;
+    a.descs = c->d_descs; a.desc_of_env = c->d_desc_of_env; a.cfg = c->rcfg; a.S = c->S; a.I = c->I; a.N = N;
+    a.ids = ids; a.n = n; a.robot = c->cfg.robot; a.first_episode = first_episode != 0; a.have_state = c->have_layout;
+    a.episode0 = (uint32_t)episode0; a.env_id0 = c->env_id0;
+    a.k0 = (uint32_t)(c->cfg.seed & 0xffffffffu); a.k1 = (uint32_t)(c->cfg.seed >> 32);
+    a.rec_f = c->st_f; a.rec_i = c->st_i; a.status = c->d_rstat; a.n_fail = counters + 1;
+    // a persistent grid: the lanes stride over the list, as many wavefronts as the LDS holds (5 per CU)
+    const int blocks = std::min((n + RS_BLOCK - 1) / RS_BLOCK, 5 * c->n_cu);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int rc = timing_events(c, &e0, &e1);
+    if (rc) return rc;
+    if (e0) HIPCHK(c, hipEventRecord(e0, c->stream));
+    hipLaunchKernelGGL(k_reset_sample, dim3(blocks), dim3(RS_BLOCK), 0, c->stream, a);
+    if (e1) HIPCHK(c, hipEventRecord(e1, c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(&n_fail, counters + 1, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  if (n > 0 && n_fail == 0) {   // install exactly as sag_set_layout does, from the staging records
+    hipLaunchKernelGGL(k_install, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->S, c->I, N, ids, n, c->st_f, c->st_i, 1);
+    hipLaunchKernelGGL(k_clear_cost, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->d_cost, ids, n);
+    hipLaunchKernelGGL(k_extract, dim3((n + 255) / 256), dim3(256), 0, c->stream, c->S, c->I, N, ids, n, c->st_f, c->st_i);
+    HIPCHK(c, hipGetLastError());
+    if (!ids) {
+      HIPCHK(c, hipMemcpyAsync(c->L_f, c->st_f, (size_t)n * SAG_REC_FLOATS * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+      HIPCHK(c, hipMemcpyAsync(c->L_i, c->st_i, (size_t)n * SAG_REC_INTS * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    } else {
+      const size_t pieces = (size_t)n * (SAG_REC_FLOATS / 4 + SAG_REC_INTS / 4);
+      hipLaunchKernelGGL(k_move_rows, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, c->stream, c->L_f, c->L_i, c->st_f,
+                         c->st_i, ids, n, 0, 0);
+      HIPCHK(c, hipGetLastError());
+    }
+    c->hot_valid = false;
+    c->ext_pending = false;
+    c->have_layout = true;
+  }
+  if (status) HIPCHK(c, hipMemcpyAsync(status, c->d_rstat, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  if (bound && c->have_layout) {
+    hipLaunchKernelGGL(k_reset_bound, dim3((N + 255) / 256), dim3(256), 0, c->stream, c->S, N, c->d_rbound);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(bound, c->d_rbound, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return n_fail;
 }
 
 int sag_step_device(sag_ctx* c, const float* d_actions, const float* d_noise, int32_t nstep, float* d_obs,

@@ -52,7 +52,7 @@ class BatchedSafeAdaptationGym:
 
   def __init__(self, robot_base, n_envs=1, rgb_observation=False, config=None, devices=None,
                parity_rng=False, device_seed=None, render_lidars_and_collision=False, render_options=None,
-               device_buffers=False):
+               device_buffers=False, device_reset=False):
     # rgb_observation: the observation is the robot camera's 64 x 64 x 3 uint8 image
     # (safe_adaptation_gym.py:122-126,148-149), ray-cast on the device
     self._rgb_observation = bool(rgb_observation)
@@ -69,6 +69,13 @@ class BatchedSafeAdaptationGym:
     self.device_buffers = bool(device_buffers)
     if self.device_buffers and self.parity_rng:
       raise ValueError('device_buffers: the reference-order host generators of parity_rng draw on the host every step')
+    # device_reset: reset() samples the new layouts on the device (sag_reset_device, throughput mode only): no record
+    # download / upload, and reset(mask=...) resets some envs only
+    self.device_reset = bool(device_reset)
+    if self.device_reset and self.parity_rng:
+      raise ValueError('device_reset: parity_rng reproduces the reference\'s host MT19937 layout stream')
+    self._last_obs = None   # device_reset, host buffers: what the last step() returned (rows kept by a masked reset)
+    self._mask_bufs = None  # device_reset: per-shard device copies of a host reset mask
     self.devices = [0] if devices is None else list(devices)
     if self.n_envs < len(self.devices):
       self.devices = self.devices[:self.n_envs]
@@ -147,11 +154,24 @@ class BatchedSafeAdaptationGym:
     self._task_ids = np.array([t.TASK_ID for t in self._tasks], np.int32)
     self._reward_dim = max(t.REWARD_DIM for t in self._tasks)
     self._persist = None  # task attributes that outlive an episode (filled by _pull_task_state)
-    self._build_world(first_episode=True)
+    if self.device_reset:
+      self._map(lambda c, s, e: c.set_tasks(self._descs, self._desc_of_env[s:e], self.base_config, env_id0=s))
+      self._reset_device(first_episode=True)
+    else:
+      self._build_world(first_episode=True)
 
-  def reset(self, *, seed=None, return_info=False, options=None):
+  def reset(self, *, seed=None, return_info=False, options=None, mask=None):
+    """mask (device_reset only): the envs to reset - a host bool / uint8 array [n_envs], or one device array of uint8
+    [n_shard] per shard (a DeviceArray such as step()'s `done` view, or any __cuda_array_interface__ array on the shard's
+    device; a list when there are several shards).  The other envs keep their state, and their rows of the returned
+    observation are what the last step() returned.  A device mask written on another stream must be complete before
+    the call (as device actions)."""
     assert self._tasks is not None or (options is not None and 'task' in options), (
         'A task should be first set before reset.')
+    if mask is not None and not self.device_reset:
+      raise ValueError('reset(mask=...) needs device_reset=True')
+    if mask is not None and options is not None and 'task' in options:
+      raise ValueError('reset(mask=...) with a new task: a task is set for the whole batch')
     self._episode += 1
     if seed is not None:
       self._base_seed = int(seed)
@@ -165,6 +185,8 @@ class BatchedSafeAdaptationGym:
     if options is not None and 'task' in options:
       self.set_task(options['task'])
       return self._observe()
+    if self.device_reset:
+      return self._reset_masked(mask) if mask is not None else (self._reset_device(first_episode=False), self._observe())[1]
     self._pull_task_state()
     self._build_world(first_episode=False)
     return self._observe()
@@ -205,6 +227,8 @@ class BatchedSafeAdaptationGym:
           rs.randint(0, 2**32, size=int(n), dtype=np.uint32)
     reward = rew if self._reward_dim == 2 else rew[:, 0]
     info = {'cost': cost, 'bound': self._bounds, 'goal_met': met}
+    if self.device_reset:
+      self._last_obs = obs.copy()
     return obs, reward, done, info
 
   # -- device-resident path (device_buffers=True) ---------------------------------------------------
@@ -288,6 +312,9 @@ class BatchedSafeAdaptationGym:
       for p in b.values():
         c.dev_free(p)
     self._dev = None
+    for c, p in zip(self._ctx, self._mask_bufs or []):
+      c.dev_free(p)
+    self._mask_bufs = None
     for c in self._ctx:
       c.close()
     if self._pool:
@@ -345,6 +372,67 @@ class BatchedSafeAdaptationGym:
     ri[:, nat.I_EPISODE] = self._episode & 0xffffff   # episode nonce of the device-side generator
     self._map(lambda c, s, e: c.set_layout(rf[s:e], ri[s:e]))
 
+  def _reset_device(self, first_episode, masks=None):
+    """World.sample_layout + World.reset on the device (sag_reset_device) for every env, or for the envs of the
+    per-shard device masks (pointers).  Failures raise ResamplingError; a shard with a failure installs nothing."""
+    masks = masks or [None] * len(self._ctx)
+    outs = self._map(lambda c, s, e: c.reset_device(first_episode, self._episode & 0xffffff,
+                                                     masks[self._ctx.index(c)]))
+    bad = np.concatenate([np.flatnonzero(st) + s for (rc, st, _), (s, e) in zip(outs, self._ranges)])
+    if bad.size:
+      raise ResamplingError(f'Failed to generate layout for envs {bad[:8].tolist()}')
+    self._bounds = np.concatenate([b for _, _, b in outs])
+
+  def _reset_masked(self, mask):
+    on_device = lambda x: isinstance(x, nat.DeviceArray) or hasattr(x, '__cuda_array_interface__')   # noqa: E731
+    if isinstance(mask, (list, tuple)) and len(mask) == len(self._ctx) and all(on_device(x) for x in mask):
+      dmasks = list(mask)
+    elif on_device(mask):
+      if len(self._ctx) != 1:
+        raise ValueError(f'{len(self._ctx)} shards: pass one device mask per shard')
+      dmasks = [mask]
+    else:
+      dmasks = None
+      hmask = np.asarray(mask)
+      if hmask.shape != (self.n_envs,) or hmask.dtype not in (np.bool_, np.uint8):
+        raise ValueError(f'mask: bool / uint8 of shape ({self.n_envs},), not {hmask.dtype} {hmask.shape}')
+      hmask = hmask.astype(np.uint8)
+    if dmasks is not None:
+      ptrs = [nat.device_pointer(m, (e - s,), c.device, np.uint8) for c, (s, e), m in zip(self._ctx, self._ranges, dmasks)]
+    else:   # a host mask travels in a buffer of each shard
+      if self._mask_bufs is None:
+        self._mask_bufs = [c.dev_alloc(e - s) for c, (s, e) in zip(self._ctx, self._ranges)]
+      for c, (s, e), buf in zip(self._ctx, self._ranges, self._mask_bufs):
+        c.dev_upload(buf, hmask[s:e])
+      ptrs = [buf.value for buf in self._mask_bufs]
+    self._reset_device(first_episode=False, masks=[nat.C.c_void_p(p) for p in ptrs])
+    # the observation: rows of reset envs are formed at their new state, the others are what the last step returned
+    if dmasks is None:
+      rows = [hmask[s:e].astype(bool) for s, e in self._ranges]
+    else:
+      rows = [c.dev_download(nat.C.c_void_p(p), (e - s,), np.uint8).astype(bool) for c, (s, e), p in zip(self._ctx, self._ranges, ptrs)]
+    if self.device_buffers:
+      bufs = self._dev_bufs()
+      for c, b, r, (s, e) in zip(self._ctx, bufs, rows, self._ranges):
+        if self._rgb_observation:   # the image is a function of the state: the kept envs render what the step rendered
+          c.render_rgb_device(b['img'])
+        else:
+          last = c.dev_download(b['obs'], (e - s, self.robot.obs_dim), np.float32)
+          last[r] = c.observe()[r]
+          c.dev_upload(b['obs'], last)
+      self.wait()
+      outs = [self._views(k)[0] for k in range(len(self._ctx))]
+      return outs[0] if len(outs) == 1 else outs
+    new = self._render_rgb() if self._rgb_observation else np.concatenate(self._map(lambda c, s, e: c.observe()))
+    r = np.concatenate(rows)
+    if self._last_obs is None or self._rgb_observation:
+      obs = new
+    else:
+      obs = self._last_obs.copy()
+      obs[r] = new[r]
+    self._last_obs = obs.copy()
+    return obs
+
   def _pull_task_state(self):
     """Task attributes that outlive an episode in the reference because they live on
     the Task object, not in the simulator: PressButtons._state (press_buttons.py:23),
@@ -368,9 +456,10 @@ class BatchedSafeAdaptationGym:
       self.wait()
       outs = [self._views(k)[0] for k in range(len(self._ctx))]
       return outs[0] if len(outs) == 1 else outs
-    if self._rgb_observation:
-      return self._render_rgb()
-    return np.concatenate(self._map(lambda c, s, e: c.observe()))
+    obs = self._render_rgb() if self._rgb_observation else np.concatenate(self._map(lambda c, s, e: c.observe()))
+    if self.device_reset:
+      self._last_obs = obs.copy()
+    return obs
 
 
 def _peek_words(rs, n):
