@@ -9,4 +9,4 @@ case "$V" in
 esac
 export SAG_LIB=$HERE/_build/libsag_hostemu_$V.so SAG_HOSTEMU=1
 export ASAN_OPTIONS=detect_leaks=0:abort_on_error=0:detect_stack_use_after_return=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=${HOSTEMU_HALT:-1}
-LD_PRELOAD=$PRE exec "$@"
+LD_PRELOAD=$PRE${LD_PRELOAD:+:$LD_PRELOAD} exec "$@"   # (the sanitizer runtime first; whatever is preloaded already stays)

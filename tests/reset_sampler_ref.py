@@ -261,3 +261,60 @@ def _records(robot, desc, cfg, it, gids, nonces, n4, k0, k1, pos, first_episode,
       rf[:, F_BUTTONS + 2 * b], rf[:, F_BUTTONS + 2 * b + 1] = x, y; b += 1
   return rf, ri
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# What the install of a NEW world (k_install with init_task, csrc/sag_device.hpp) derives from a sampled record
+# ---------------------------------------------------------------------------------------------------------------------
+F_LAST, MAX_VASES, BUTTON_R = 38, 10, np.float32(0.1)
+TASK_COLLECT, TASK_PRESS_BUTTONS, TASK_PRESS_BUTTONS_SCARCE = 1, 8, 9
+BOX_BOUND = {1: np.float32(0.42426406871192851), 2: np.float32(0.31048349392520047), 3: np.float32(0.14)}   # box, rod, ball
+
+
+def install_last(rf, ri):
+  """task.reset's `last` distances (record floats 38-40) of installed records: fp64 from the fp32 positions, stored fp32."""
+  rf = np.asarray(rf, np.float32)
+  d = lambda a, b: np.sqrt((rf[:, a].astype(np.float64) - rf[:, b]) ** 2 + (rf[:, a + 1].astype(np.float64) - rf[:, b + 1]) ** 2)  # noqa: E731
+  out = rf[:, F_LAST:F_LAST + 3].copy()
+  task = ri[:, I_TASK]
+  buttons = (task == TASK_PRESS_BUTTONS) | (task == TASK_PRESS_BUTTONS_SCARCE)
+  gb = F_BUTTONS + 2 * ri[:, I_GOAL_BUTTON]
+  rows = np.arange(len(rf))
+  to_button = np.sqrt((rf[:, F_ROBOT].astype(np.float64) - rf[rows, gb]) ** 2 + (rf[:, F_ROBOT + 1].astype(np.float64) - rf[rows, gb + 1]) ** 2)
+  out[:, 0] = np.where(buttons, to_button, np.where(task != TASK_COLLECT, d(F_ROBOT, F_GOAL), out[:, 0]))
+  box = ri[:, I_BOX_KIND] != 0
+  out[box, 2] = d(F_GOAL, F_BOX)[box]
+  out[box, 1] = d(F_ROBOT, F_BOX)[box]
+  return out
+
+
+def install_awake(rf, ri):
+  """SAG_I_AWAKE of installed records: bit a (vases 0-9, the task object 10) is set when body a moves or its bounding circle
+  overlaps another free body's, a pillar's or a button's - in the install's fp32 arithmetic."""
+  rf = np.asarray(rf, np.float32)
+  n = len(rf)
+  vsz, psz = rf[:, F_VASE_SIZE], rf[:, F_PILLAR_SIZE]
+  col = lambda a: F_VASES + 6 * a if a < MAX_VASES else F_BOX   # noqa: E731
+  exists = lambda a: ri[:, I_NV] > a if a < MAX_VASES else ri[:, I_BOX_KIND] != 0   # noqa: E731
+
+  def bound(a):
+    if a < MAX_VASES:
+      return vsz * np.float32(1.41421356237309504880)
+    return np.select([ri[:, I_BOX_KIND] == k for k in (1, 2, 3)], [np.full(n, BOX_BOUND[k], np.float32) for k in (1, 2, 3)], np.float32(0))
+
+  def closer(a, x, y, r):
+    dx, dy, rs = x - rf[:, col(a)], y - rf[:, col(a) + 1], bound(a) + r
+    return dx * dx + dy * dy < rs * rs
+
+  awake = np.zeros(n, np.int32)
+  for a in range(MAX_VASES + 1):
+    over = (rf[:, col(a) + 3:col(a) + 6] != 0).any(1)
+    for b in range(MAX_VASES + 1):
+      if b != a:
+        over |= exists(b) & closer(a, rf[:, col(b)], rf[:, col(b) + 1], bound(b))
+    for q in range(2):
+      over |= (ri[:, I_NP] > q) & closer(a, rf[:, F_PILLARS + 2 * q], rf[:, F_PILLARS + 2 * q + 1], psz)
+    for q in range(6):
+      over |= (ri[:, I_NB] > q) & closer(a, rf[:, F_BUTTONS + 2 * q], rf[:, F_BUTTONS + 2 * q + 1], BUTTON_R)
+    awake |= (over & exists(a)).astype(np.int32) << a
+  return awake

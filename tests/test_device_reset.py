@@ -57,6 +57,20 @@ def _assert_records(got_f, got_i, ref_f, ref_i, maxulp=0):
     np.testing.assert_array_equal(got_f[:, keep_f], ref_f[:, keep_f])
 
 
+def _assert_installed(nat, robot, got_f, got_i):
+  """What _assert_records leaves out - the `last` distances and the awake flags, computed by the install - against the
+  restatement of the install (R.install_last / R.install_awake) and against a fresh context given the same records with
+  sag_set_layout (the install twin): every float and int comes back identical."""
+  np.testing.assert_array_max_ulp(got_f[:, LAST], R.install_last(got_f, got_i), maxulp=1)
+  np.testing.assert_array_equal(got_i[:, AWAKE], R.install_awake(got_f, got_i))
+  tw = nat.Context(robot, len(got_f), seed=KEY)
+  tw.set_layout(got_f, got_i)
+  tf, ti = tw.get_state()
+  tw.close()
+  np.testing.assert_array_equal(tf, got_f)
+  np.testing.assert_array_equal(ti, got_i)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # CPU
 # ---------------------------------------------------------------------------------------------------------------------
@@ -147,6 +161,8 @@ from safe_adaptation_gym_amd import _native as nat
 out, key = sys.argv[1], int(sys.argv[2])
 res = {}
 cases = [('point', list(range(14)), 64), ('car', [10], 64), ('doggo', [7], 64)]
+if sys.argv[3:] == ['masked']:   # the masked part only (the sanitizer build)
+  cases = []
 for robot, tasks, per in cases:
   descs = [nat.task_desc_default(t) for t in tasks]
   doe = np.repeat(np.arange(len(tasks)), per).astype(np.int32)
@@ -159,6 +175,25 @@ for robot, tasks, per in cases:
   res.update({robot + '_f0': f0, robot + '_i0': i0, robot + '_f1': f1, robot + '_i1': i1,
               robot + '_rc': np.array([rc0, rc1]), robot + '_b1': b1})
   c.close()
+# a masked reset and a replay by ids on a ragged batch: the list, scatter and gather kernels (k_reset_list, k_move_rows, k_install with ids)
+n = 64 * 2 + 3
+descs = [nat.task_desc_default(t) for t in (3, 7, 10)]
+c = nat.Context('point', n, seed=key)
+c.set_tasks(descs, (np.arange(n) % 3).astype(np.int32), None, env_id0=1000)
+rc0 = c.reset_device(True, episode0=77)[0]
+fa, ia = c.get_state()
+m = np.where(np.arange(n) * 7 % 5 < 2, 255, 0).astype(np.uint8)
+m[0], m[-1] = 0, 2
+p = c.dev_alloc(n)
+c.dev_upload(p, m)
+rc1, st1, b1 = c.reset_device(False, d_mask=p)
+fb, ib = c.get_state()
+c.reset(np.array([n - 1, 3, 64, 0], np.int32))
+fc, ic = c.get_state()
+c.dev_free(p)
+c.close()
+res.update(masked_m=m, masked_rc=np.array([rc0, rc1]), masked_st=st1, masked_b=b1, masked_fa=fa, masked_ia=ia, masked_fb=fb,
+           masked_ib=ib, masked_fc=fc, masked_ic=ic)
 np.savez(out, **res)
 '''
 
@@ -185,6 +220,51 @@ def test_host_build_of_the_kernel_equals_the_restatement(tmp_path):
     rf1, ri1, st1 = _ref_batch(robot, descs, doe, cfg, gids, np.full(len(doe), 78), KEY, False, _prev(z[robot + '_f0'], z[robot + '_i0']))
     _assert_records(z[robot + '_f1'], z[robot + '_i1'], rf1, ri1)
     np.testing.assert_array_equal(z[robot + '_b1'], rf1[:, R.F_BOUND])
+  _check_masked(z, cfg)
+
+
+def _check_masked(z, cfg):
+  """The masked call of HOSTEMU_RUN on 64 * 2 + 3 envs: rows outside the mask untouched, rows inside the restatement's with
+  what the install adds (`last`, awake flags: R.install_last / R.install_awake); the replay by ids restores what each env
+  last received."""
+  n = 64 * 2 + 3
+  m = z['masked_m'] != 0
+  assert m[-1] and not m[0] and 0 < m.sum() < n and list(z['masked_rc']) == [0, 0] and not z['masked_st'].any()
+  descs = [_nat().task_desc_default(t) for t in (3, 7, 10)]
+  doe, gids = np.arange(n) % 3, 1000 + np.arange(n)
+  fa, ia, fb, ib, fc, ic = (z['masked_' + k] for k in ('fa', 'ia', 'fb', 'ib', 'fc', 'ic'))
+  np.testing.assert_array_equal(fb[~m], fa[~m])
+  np.testing.assert_array_equal(ib[~m], ia[~m])
+  rf, ri, st = _ref_batch('point', descs, doe[m], cfg, gids[m], np.full(m.sum(), 78), KEY, False, _prev(fa[m], ia[m]))
+  _assert_records(fb[m], ib[m], rf, ri)
+  np.testing.assert_array_equal(fb[m][:, LAST], R.install_last(fb[m], ib[m]))
+  np.testing.assert_array_equal(ib[m, AWAKE], R.install_awake(fb[m], ib[m]))
+  np.testing.assert_array_equal(z['masked_b'], fb[:, R.F_BOUND])
+  ids = np.array([n - 1, 3, 64, 0])
+  want_f, want_i = fb.copy(), ib.copy()
+  want_i[ids, R.I_EPISODE] += 1
+  np.testing.assert_array_equal(fc, want_f)   # (no step in between: the layout an env last received is its state)
+  np.testing.assert_array_equal(ic, want_i)
+
+
+def test_masked_reset_kernels_on_the_sanitizer_build(tmp_path):
+  """The masked part of HOSTEMU_RUN on the ASan / UBSan host build of the library's sources (tests/hostemu/run.sh's clang
+  build, here in the CPU suite): the list, scatter and gather kernels index staging rows, the layout store and the SoA state
+  by env id - no sanitizer report, and the same records."""
+  import build as hb   # tests/hostemu/build.py
+  if not os.path.exists(hb.CLANG):
+    pytest.fail('no clang for the host build of the kernel')
+  lib = hb.build('clang', False, True, [], False, False, 'san')
+  env = dict(os.environ, SAG_LIB=lib, SAG_HOSTEMU='1', PYTHONPATH=ROOT + os.pathsep + os.path.join(ROOT, 'tests'),
+             ASAN_OPTIONS='detect_leaks=0:abort_on_error=0:detect_stack_use_after_return=0:halt_on_error=1',
+             UBSAN_OPTIONS='print_stacktrace=1:halt_on_error=1')
+  # the sanitizer runtime first; whatever is preloaded already stays
+  env['LD_PRELOAD'] = os.pathsep.join([hb.preload('clang')] + ([os.environ['LD_PRELOAD']] if os.environ.get('LD_PRELOAD') else []))
+  out = str(tmp_path / 'rec.npz')
+  r = subprocess.run([sys.executable, '-c', HOSTEMU_RUN, out, str(KEY), 'masked'], env=env, capture_output=True, text=True, timeout=900)
+  assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+  assert 'Sanitizer' not in r.stderr and 'runtime error' not in r.stderr, r.stderr[-3000:]
+  _check_masked(np.load(out), _cfg())
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -216,11 +296,13 @@ def test_device_records_equal_the_restatement(nat, robot):
   f0, i0 = c.get_state()
   rf, ri, _ = _ref_batch(robot, descs, doe, _cfg(), gids, np.full(len(doe), 9), KEY, True)
   _assert_records(f0, i0, rf, ri, maxulp=1)
+  _assert_installed(nat, robot, f0, i0)
   np.testing.assert_array_equal(b, f0[:, R.F_BOUND])
   rc, st, b = c.reset_device(False)
   f1, i1 = c.get_state()
   rf1, ri1, _ = _ref_batch(robot, descs, doe, _cfg(), gids, np.full(len(doe), 10), KEY, False, _prev(f0, i0))
   _assert_records(f1, i1, rf1, ri1, maxulp=1)
+  _assert_installed(nat, robot, f1, i1)
   c.close()
 
 
@@ -233,6 +315,7 @@ def test_device_records_with_ctrl_range_scale_and_random_bound(nat):
   f0, i0 = c.get_state()
   rf, ri, _ = _ref_batch('doggo', descs, doe, _cfg(**config), np.arange(len(doe)), np.full(len(doe), 3), KEY, True)
   _assert_records(f0, i0, rf, ri, maxulp=1)
+  _assert_installed(nat, 'doggo', f0, i0)
   assert len(np.unique(f0[:, R.F_BOUND])) > 200 and (f0[:, R.F_CTRL_SCALE:R.F_CTRL_SCALE + 12] != 1).all()
   c.close()
 
@@ -327,6 +410,7 @@ def _masked_run(device_buffers):
   d = env._descs[0]
   rf, ri, st = R.sample('point', d, _cfg(), np.flatnonzero(m), i1[m, R.I_EPISODE], env._base_seed, False, _prev(f0[m], i0[m]))
   _assert_records(f1[m], i1[m], rf, ri, maxulp=1)
+  _assert_installed(nat, 'point', f1[m], i1[m])
   env.close()
 
 
@@ -354,9 +438,9 @@ def test_device_layout_installs_like_set_layout_and_replays(nat):
   np.testing.assert_array_equal(c.get_state()[0], d.get_state()[0])
   c.reset()   # sag_reset replays the device-drawn layout with the next nonce
   f3, i3 = c.get_state()
-  keep = np.setdiff1d(np.arange(R.REC_FLOATS), LAST)
-  np.testing.assert_array_equal(f3[:, keep], rf[:, keep])
-  assert (i3[:, R.I_EPISODE] == ri[:, R.I_EPISODE] + 1).all()
+  np.testing.assert_array_equal(f3, rf)   # (`last` distances included: the layout store keeps the records as installed)
+  ri[:, R.I_EPISODE] += 1
+  np.testing.assert_array_equal(i3, ri)   # (install-time awake flags included)
   c.close(); d.close()
 
 

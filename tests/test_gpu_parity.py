@@ -312,7 +312,7 @@ def _draw_counts(nat, ri, o_met, o_used):
   return np.array([resample.sum(), radius.sum(), button.sum(), o_used.sum()], np.int64)
 
 
-def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
+def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False, resets=None, config=None):
   """Every step: take the device state, advance the device AND both oracle builds (fp64 =
   the specification, fp32 = same source in the device's precision) from it with identical
   action / noise / random tape, compare outputs and next state, continue from the device.
@@ -327,7 +327,17 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
   env-steps.  Discrete outputs (goal_met, done, RNG words consumed, task ints) are exact;
   cost flags are exact except where the oracle reports the decision within 1e-5 of its
   threshold.  Observations are checked as a function of the device's own post-step state (tight) and end to
-  end against the oracle's within the bound that the actual state difference implies (_lidar_e2e_bound)."""
+  end against the oracle's within the bound that the actual state difference implies (_lidar_e2e_bound).
+
+  resets = {step: 'events' | 'random'} (throughput only): the layouts are drawn on the device (sag_set_tasks + sag_reset_device,
+  world config `config`)
+  instead of installed from host records, and after each of these steps a masked device reset starts new episodes for the envs
+  whose goal was met or that paid a cost in their current episode / for a random 30 %.  The oracle legs then start the new episodes from the
+  device's records with what the install derives - the `last` distances and the awake flags - replaced by the restatement's
+  fp64 values (reset_sampler_ref.install_last / install_awake), so a wrong `last` shows in the first reward and a missed flag
+  in the first state; the same rules, tolerances and budgets apply, and the env-steps right after a reset are also counted on
+  their own."""
+  assert not resets or throughput
   n, T = (130, 120) if throughput else (192 * scale, 160)
   rid = {'point': 0, 'car': 1}[robot]
   od = 60 if robot == 'point' else 72
@@ -342,7 +352,19 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
   if task not in ('haul_box',):
     rf = bu.goal_beyond_box(rf, ri)
   ctx = nat.Context(robot, n, seed=TP_SEED if throughput else 1234)
-  ctx.set_layout(rf, ri)
+  if resets:
+    import reset_sampler_ref as R
+    tids = ri[:, nat.I_TASK]   # (the host records name the tasks only)
+    uniq, doe = np.unique(tids, return_inverse=True)
+    ctx.set_tasks([nat.task_desc_default(int(k)) for k in uniq], doe.astype(np.int32), config, env_id0=0)
+    rc, st, _ = ctx.reset_device(True, episode0=1)
+    assert rc == 0 and not st.any()
+    d_mask = ctx.dev_alloc(n)
+  else:
+    ctx.set_layout(rf, ri)
+  fresh = np.zeros(n, bool)   # envs whose episode a masked reset has just started
+  events = np.zeros(n, bool)  # envs whose goal was met or that paid a cost in their current episode
+  fresh64 = fresh32 = fresh_steps = 0
   rng = np.random.RandomState(7)
   mt = np.random.RandomState(99)
   obs0 = ctx.observe()
@@ -356,6 +378,10 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
   bad64_env, bad32_env = np.zeros(n, int), np.zeros(n, int)
   for t in range(T):
     rf, ri = ctx.get_state()
+    if fresh.any():
+      np.testing.assert_array_max_ulp(rf[fresh, 38:41], R.install_last(rf[fresh], ri[fresh]), maxulp=1)
+      np.testing.assert_array_equal(ri[fresh, nat.I_AWAKE], R.install_awake(rf[fresh], ri[fresh]))
+      rf[fresh, 38:41], ri[fresh, nat.I_AWAKE] = R.install_last(rf[fresh], ri[fresh]), R.install_awake(rf[fresh], ri[fresh])
     arr, arr32 = oracle.make_batch(rf, ri), oracle32.make_batch(rf, ri)
     act = bu.pursuit_actions(rf, ri, rng, robot=robot)
     noise = mt.normal(size=(n, 2)).astype(np.float32)
@@ -396,6 +422,7 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
     viol64 += int(bad64.sum())
     viol32 += int(bad32.sum())
     bad64_env += bad64; bad32_env += bad32
+    fresh64 += int(bad64[fresh].sum()); fresh32 += int(bad32[fresh].sum()); fresh_steps += int(fresh.sum())
     ok = ~bad64
     # discrete outputs
     np.testing.assert_array_equal(d_done, o_done)
@@ -430,7 +457,27 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
     np.testing.assert_allclose(d_rew[ok], o_rew[ok], rtol=0, atol=2e-4, err_msg=f'reward step {t}')
     n_met += int(d_met.sum())
     n_cost += int(d_cost.sum())
-  assert n_met > (5 if ri[:, 5].any() else 20), 'the rollout should exercise goal-met events'
+    fresh = np.zeros(n, bool)
+    events |= (d_met != 0) | (d_cost != 0)
+    if resets and t in resets:
+      fresh = events.copy() if resets[t] == 'events' else rng.uniform(size=n) < 0.3
+      assert fresh.any(), f'the mask after step {t} is empty'
+      events &= ~fresh
+      ctx.dev_upload(d_mask, fresh.astype(np.uint8))
+      rc, st, _ = ctx.reset_device(False, d_mask=d_mask)
+      assert rc == 0 and not st.any()
+      r_rf, r_ri = ctx.get_state()
+      np.testing.assert_array_equal(r_rf[~fresh], d_rf[~fresh])
+      np.testing.assert_array_equal(r_ri[~fresh], d_ri[~fresh])
+      assert (r_ri[fresh, nat.I_STEP] == 0).all() and (r_ri[fresh, nat.I_EPISODE] == (d_ri[fresh, nat.I_EPISODE] + 1) & 0xffffff).all()
+  if resets:
+    # device-drawn layouts cannot be arranged for goals (goal_beyond_box): the episodes the resets start are what must be exercised
+    ctx.dev_free(d_mask)
+    assert fresh_steps >= 0.3 * n, f'{fresh_steps} first steps of new episodes compared'
+    _log_lockstep(f'{robot}/{task} across {len(resets)} masked device resets: {fresh_steps} first steps of new episodes, of which outside the stated '
+                  f'tolerance vs fp64 oracle {fresh64}, vs fp32 oracle {fresh32}')
+  else:
+    assert n_met > (5 if ri[:, 5].any() else 20), 'the rollout should exercise goal-met events'
   assert n_cost > 20, 'the rollout should exercise cost events'
   assert n_near <= 0.001 * n * T
   # Budgets per TASK, at ~2-3x the measured counts (profiles/r04_lockstep_counts.txt; round 3: Point tasks <= 3 of 30 720
@@ -465,8 +512,8 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False):
   if throughput:
     _log_lockstep(f'{robot}/{task} throughput mode: in-step draws by the device generator - goal resamples {draws[0]}, CatchGoal '
                   f'radius redraws {draws[1]}, goal-button choices {draws[2]}, words {draws[3]}')
-    has = lambda *ids: np.isin(ri[:, nat.I_TASK], ids).any()   # noqa: E731
-    if (~np.isin(ri[:, nat.I_TASK], [1, 8, 9])).any():
+    has = lambda *ids: np.isin(ri[:, nat.I_TASK], ids).any() and not resets   # noqa: E731  (resets: device-drawn layouts, see above)
+    if (~np.isin(ri[:, nat.I_TASK], [1, 8, 9])).any() and not resets:
       assert draws[0] > 0, 'no goal was resampled'
     if has(0):
       assert draws[1] > 0, 'no CatchGoal radius was redrawn'
@@ -1080,7 +1127,7 @@ def test_doggo_lockstep_throughput_vs_oracle(nat, oracle):
   _doggo_lockstep(nat, oracle, MIXED, throughput=True)
 
 
-def _doggo_lockstep(nat, oracle, task, throughput=False):
+def _doggo_lockstep(nat, oracle, task, throughput=False, reset_after=None):
   """Same protocol as test_step_lockstep_vs_oracle for the Doggo robot (BASELINE config 4 shape
   for 'multitask').  Stated tolerance after one step (12 substeps) from identical fp32 state:
   robot qpos within 2e-5, qvel within 2e-3 abs + 2e-3 rel of the fp64 oracle (the device solves the
@@ -1090,7 +1137,12 @@ def _doggo_lockstep(nat, oracle, task, throughput=False):
   bounded.  goal_met / done / task ints / RNG words exact on rows inside the tolerance.
   `multitask-4096` is BASELINE config 4 at its stated size per rank (4096 envs, ~290 per task, 14 steps: VERDICT r3
   item 2), the oracle on every host core.  Cost flags that differ away from any threshold are counted over the WHOLE
-  run (round 3 allowed one per step) and budgeted at 2 - 3 x the measured count (profiles/r04_lockstep_counts.txt)."""
+  run (round 3 allowed one per step) and budgeted at 2 - 3 x the measured count (profiles/r04_lockstep_counts.txt).
+  reset_after = a step (throughput only): the layouts are drawn on the device (sag_set_tasks + sag_reset_device) and after that
+  step a masked device reset starts a new episode for a random 30 % of the envs; the oracle continues from the device's
+  records (a Doggo record has no install-derived field the step reads before writing it except `last`, replaced by the
+  restatement's fp64 value as in _lockstep)."""
+  assert reset_after is None or throughput
   n, T = (4096, 14) if task == DOGGO_C4 else (70, 30) if throughput else (64, 30)
   from safe_adaptation_gym_amd import benchmark
   if task == DOGGO_C4:
@@ -1101,7 +1153,15 @@ def _doggo_lockstep(nat, oracle, task, throughput=False):
     names = task
   rf, ri = bu.sample_records_native('doggo', names, n, seed=666)
   ctx = nat.Context('doggo', n, seed=TP_SEED if throughput else 4321)
-  ctx.set_layout(rf, ri)
+  if reset_after is not None:
+    import reset_sampler_ref as R
+    uniq, doe = np.unique(ri[:, nat.I_TASK], return_inverse=True)
+    ctx.set_tasks([nat.task_desc_default(int(k)) for k in uniq], doe.astype(np.int32), None, env_id0=0)
+    rc, st, _ = ctx.reset_device(True, episode0=1)
+    assert rc == 0 and not st.any()
+  else:
+    ctx.set_layout(rf, ri)
+  fresh = np.zeros(n, bool)
   mt = np.random.RandomState(5)
   obs0 = ctx.observe()
   rf, ri = ctx.get_state()
@@ -1115,6 +1175,11 @@ def _doggo_lockstep(nat, oracle, task, throughput=False):
   touched = flag_mism = flag_near = overflow = 0
   for t in range(T):
     rf, ri = ctx.get_state()
+    if fresh.any():
+      np.testing.assert_array_max_ulp(rf[fresh, 38:41], R.install_last(rf[fresh], ri[fresh]), maxulp=1)
+      np.testing.assert_array_equal(ri[fresh, nat.I_AWAKE], R.install_awake(rf[fresh], ri[fresh]))
+      rf[fresh, 38:41], ri[fresh, nat.I_AWAKE] = R.install_last(rf[fresh], ri[fresh]), R.install_awake(rf[fresh], ri[fresh])
+      fresh = np.zeros(n, bool)
     arr = oracle.make_batch(rf, ri)
     act = mt.uniform(-1, 1, size=(n, 12)).astype(np.float32)
     if t < 3:
@@ -1166,6 +1231,17 @@ def _doggo_lockstep(nat, oracle, task, throughput=False):
     np.testing.assert_allclose(d_obs[ok, 60:68], o_obs[ok, 60:68], rtol=2e-2, atol=2e-3, err_msg=f'touch step {t}')
     np.testing.assert_allclose(d_rew[ok], o_rew[ok], rtol=0, atol=2e-4, err_msg=f'reward step {t}')
     touched += int((d_obs[:, 60:68] > 0).any(1).sum())
+    if t == reset_after:
+      fresh = mt.uniform(size=n) < 0.3
+      d_mask = ctx.dev_alloc(n)
+      ctx.dev_upload(d_mask, fresh.astype(np.uint8))
+      rc, st, _ = ctx.reset_device(False, d_mask=d_mask)
+      ctx.dev_free(d_mask)
+      assert rc == 0 and not st.any() and fresh.sum() > n // 6
+      r_rf, r_ri = ctx.get_state()
+      np.testing.assert_array_equal(r_rf[~fresh], d_rf[~fresh])
+      np.testing.assert_array_equal(r_ri[~fresh], d_ri[~fresh])
+      assert (r_ri[fresh, nat.I_STEP] == 0).all() and (r_ri[fresh, nat.I_EPISODE] == (d_ri[fresh, nat.I_EPISODE] + 1) & 0xffffff).all()
   # cost flags differing away from any threshold, over the whole run: a contact whose penetration changes sign with the
   # rounding (fp32 planar world on the device, fp64 in the oracle).  Measured (profiles/r04_lockstep_counts.txt): 0 of
   # 57 344 env-steps at config 4's size, 0 - 1 of 1920 in the small cases; budget 1e-4 of the env-steps, at least 2.

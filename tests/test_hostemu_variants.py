@@ -6,7 +6,8 @@ because they compare two BUILDS:
     real contact and only a tolerance-based lockstep case that happens to hit the pair would notice);
   * the 64-lane projected Gauss-Seidel path of the Doggo kernel (envs with more than 32 constraint rows - rare), forced
     onto ordinary states by -DSAG_DC_FAST_ROWS=8, against the 32-lane path, one step at a time from identical state.
-The builds are unsanitized (-O1, ~30 s each, in parallel); the sanitizer builds stay a manual tool (tests/hostemu/run.sh)."""
+The builds are unsanitized (-O1, ~30 s each, in parallel); the sanitizer builds stay a manual tool (tests/hostemu/run.sh), but for
+the masked device reset (test_device_reset.py::test_masked_reset_kernels_on_the_sanitizer_build)."""
 import os
 import subprocess
 import sys
