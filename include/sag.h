@@ -388,6 +388,37 @@ int sag_set_tasks(sag_ctx* ctx, const sag_task_desc* descs, int32_t n_descs, con
 int sag_reset_device(sag_ctx* ctx, int32_t first_episode, int32_t episode0, const uint8_t* d_mask, int32_t* status,
                      float* bound);
 
+/* ---- the rollout loop on the context stream (throughput mode) ----------------------------------
+ * step -> episode bookkeeping -> masked reset of the envs that ended -> step, without a host wait or copy:
+ *   sag_step_device(..., d_obs, d_reward, d_cost, d_done, d_goal_met);
+ *   sag_episode_track_device(ctx, d_reward, d_cost, d_done, d_goal_met, max_steps, d_ended, d_episode);
+ *   sag_reset_device_async(ctx, d_ended, d_obs);
+ *
+ * sag_reset_device_async: stream-ordered form of sag_reset_device(first_episode = 0): needs sag_set_tasks and an installed
+ * layout.  Enqueued on the context stream, returns without waiting, no host copy.  d_mask as in sag_reset_device (NULL:
+ * every env).  d_obs: [n_envs][obs_dim] f32 device buffer (16-byte aligned for the Doggo) or NULL; the rows of the envs
+ * that were reset receive the observation of their new state (what sag_observe returns for them), no other row is written.
+ * Commit is per env: an env whose sampling fails keeps its state, nonce, layout-store row, observation row and episode
+ * accumulators, and bit 0 of its SAG_I_FLAGS is set (the ResamplingError bit).  No timing events are recorded
+ * (sag_kernel_time_ms stays the step's figure).  Pending external contacts (sag_set_ext_contacts) are always dropped: the
+ * host cannot know whether the mask was empty. */
+int sag_reset_device_async(sag_ctx* ctx, const uint8_t* d_mask, float* d_obs);
+/* Envs reset / envs whose sampling failed by sag_reset_device_async since the last call with clear != 0.
+ * Synchronises the stream. */
+int sag_reset_device_counts(sag_ctx* ctx, int32_t clear, uint64_t* n_reset, uint64_t* n_failed);
+
+/* Episode bookkeeping after a step, on the context stream, all pointers device pointers [n_envs]
+ * (d_reward [n_envs][2], column 0 is accumulated; d_episode [n_envs][4], 16-byte aligned).  Per env: ret += reward (one
+ * fp32 add), cost += cost != 0, length += 1, goals += goal_met != 0;
+ * ended = done ? 1 : (max_steps > 0 && length >= max_steps ? 2 : 0); d_ended[i] = ended (usable as a reset mask as it is).
+ * If ended, d_episode[i] = {ret, cost, length, goals} as four floats and the accumulators return to zero.  Rows of envs
+ * that did not end are not written.  The accumulators (one float4 per env) are allocated and zeroed on first use;
+ * sag_reset_device_async zeroes those of the envs it commits. */
+int sag_episode_track_device(sag_ctx* ctx, const float* d_reward, const uint8_t* d_cost, const uint8_t* d_done,
+                             const uint8_t* d_goal_met, int32_t max_steps, uint8_t* d_ended, float* d_episode);
+/* Zero the accumulators of the masked envs (NULL: all), stream-ordered. */
+int sag_episode_clear(sag_ctx* ctx, const uint8_t* d_mask);
+
 #ifdef __cplusplus
 }
 #endif

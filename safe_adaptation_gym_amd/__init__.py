@@ -18,7 +18,9 @@ def make(robot_name: str,
          devices=None,
          parity_rng: bool = False,
          device_buffers: bool = False,
-         device_reset: bool = False):
+         device_reset: bool = False,
+         time_limit: Optional[int] = None,
+         auto_reset: bool = False):
   from safe_adaptation_gym_amd.benchmark import ROBOTS_BASENAMES, TASKS
   from safe_adaptation_gym_amd.envs import BatchedSafeAdaptationGym
   env = BatchedSafeAdaptationGym(
@@ -30,6 +32,8 @@ def make(robot_name: str,
       parity_rng=parity_rng,
       device_buffers=device_buffers,
       device_reset=device_reset,
+      time_limit=time_limit,
+      auto_reset=auto_reset,
       render_lidars_and_collision=render_lidar_and_collision,
       render_options=render_options)
   env.seed(seed)

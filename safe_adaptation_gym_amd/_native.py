@@ -33,7 +33,8 @@ EXPORTS = [
     'sag_observe', 'sag_set_ext_contacts', 'sag_lidar_cost', 'sag_lidar_cost_device', 'sag_set_seed', 'sag_dev_alloc', 'sag_dev_free', 'sag_dev_upload',
     'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_debug_doggo_coop',
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
-    'sag_set_tasks', 'sag_reset_device'
+    'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
+    'sag_episode_clear'
 ]
 
 
@@ -108,6 +109,10 @@ def load():
                                      C.c_int32, fp, ip, up, ip, ip, C.POINTER(C.c_double), ip, C.c_int32]
   lib.sag_set_tasks.argtypes = [vp, vp, C.c_int32, ip, C.POINTER(WorldConfig), C.c_int32]
   lib.sag_reset_device.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, fp]
+  lib.sag_reset_device_async.argtypes = [vp, vp, vp]
+  lib.sag_reset_device_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+  lib.sag_episode_track_device.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp]
+  lib.sag_episode_clear.argtypes = [vp, vp]
   _lib = lib
   return lib
 
@@ -434,6 +439,26 @@ class Context:
     if rc < 0:
       self._check(rc, 'sag_reset_device')
     return rc, status, bound
+
+  def reset_device_async(self, d_mask, d_obs=None):
+    """sag_reset_device_async: a later-episode masked device reset enqueued on the context stream - no wait, no host copy.
+    d_mask: device pointer of [n_envs] bytes or None (every env); d_obs: device pointer of [n_envs][obs_dim] f32 whose rows
+    of the reset envs receive their first observation, or None.  Failures are data: reset_counts()."""
+    self._check(self.lib.sag_reset_device_async(self.h, d_mask, d_obs), 'sag_reset_device_async')
+
+  def reset_counts(self, clear=False):
+    """(envs reset, envs whose sampling failed) by reset_device_async since the last clear; joins the stream."""
+    a, b = C.c_uint64(), C.c_uint64()
+    self._check(self.lib.sag_reset_device_counts(self.h, int(bool(clear)), C.byref(a), C.byref(b)), 'sag_reset_device_counts')
+    return a.value, b.value
+
+  def episode_track(self, d_reward, d_cost, d_done, d_met, max_steps, d_ended, d_episode):
+    """sag_episode_track_device: the episode bookkeeping of one step on device buffers, enqueued on the context stream."""
+    self._check(self.lib.sag_episode_track_device(self.h, d_reward, d_cost, d_done, d_met, int(max_steps), d_ended, d_episode),
+                'sag_episode_track_device')
+
+  def episode_clear(self, d_mask=None):
+    self._check(self.lib.sag_episode_clear(self.h, d_mask), 'sag_episode_clear')
 
   def set_seed(self, seed):
     """Key of the device-side generator of throughput mode (env.seed())."""

@@ -20,6 +20,7 @@
 
 #include "sag_device.hpp"
 #include "sag_reset.hpp"
+#include "sag_rollout.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -101,6 +102,8 @@ struct sag_ctx {
   bool have_tasks = false;
   int32_t* d_rstat = nullptr;   // [N] status by env, then 2 counters (listed envs, failures)
   float* d_rbound = nullptr;    // [N]
+  unsigned long long* d_rtot = nullptr;   // sag_reset_device_async: envs reset, envs whose sampling failed (sag_reset_device_counts)
+  float* d_acc = nullptr;       // [N] float4 episode accumulators (sag_episode_track_device), allocated on first use
   std::string err;
 };
 
@@ -558,7 +561,7 @@ int sag_destroy(sag_ctx* c) {
   for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   void* bufs[] = {c->S, c->I, c->G, c->d_rows, c->d_count, c->d_kind, c->L_f, c->L_i, c->st_f, c->st_i, c->st_ids, c->d_act, c->d_noise,
                   c->d_tape, c->d_obs, c->d_rew, c->d_cost, c->d_done, c->d_met, c->d_used, c->scratch, c->d_rgb, c->d_dr, c->d_dg_sched, c->d_hot,
-                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound};
+                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
@@ -713,6 +716,10 @@ int sag_set_tasks(sag_ctx* c, const sag_task_desc* descs, int32_t n_descs, const
   if (!c->d_desc_of_env) HIPCHK(c, hipMalloc(&c->d_desc_of_env, (size_t)c->N * sizeof(int32_t)));
   if (!c->d_rstat) HIPCHK(c, hipMalloc(&c->d_rstat, ((size_t)c->N + 2) * sizeof(int32_t)));
   if (!c->d_rbound) HIPCHK(c, hipMalloc(&c->d_rbound, (size_t)c->N * sizeof(float)));
+  if (!c->d_rtot) {
+    HIPCHK(c, hipMalloc(&c->d_rtot, 2 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->d_rtot, 0, 2 * sizeof(unsigned long long), c->stream));
+  }
   HIPCHK(c, hipMemcpyAsync(c->d_descs, descs, (size_t)n_descs * sizeof(sag_task_desc), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_desc_of_env, desc_of_env, (size_t)c->N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // the host arrays are the caller's
@@ -743,7 +750,7 @@ int sag_reset_device(sag_ctx* c, int32_t first_episode, int32_t episode0, const 
   if (n > 0) {
     ResetArgs a;
     a.descs = c->d_descs; a.desc_of_env = c->d_desc_of_env; a.cfg = c->rcfg; a.S = c->S; a.I = c->I; a.N = N;
-    a.ids = ids; a.n = n; a.robot = c->cfg.robot; a.first_episode = first_episode != 0; a.have_state = c->have_layout;
+    a.ids = ids; a.n = n; a.n_dev = nullptr; a.robot = c->cfg.robot; a.first_episode = first_episode != 0; a.have_state = c->have_layout;
     a.episode0 = (uint32_t)episode0; a.env_id0 = c->env_id0;
     a.k0 = (uint32_t)(c->cfg.seed & 0xffffffffu); a.k1 = (uint32_t)(c->cfg.seed >> 32);
     a.rec_f = c->st_f; a.rec_i = c->st_i; a.status = c->d_rstat; a.n_fail = counters + 1;
@@ -785,6 +792,134 @@ int sag_reset_device(sag_ctx* c, int32_t first_episode, int32_t episode0, const 
   }
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return n_fail;
+}
+
+// episode accumulators: one float4 per env, allocated and zeroed (stream-ordered) on first use
+static int ensure_acc(sag_ctx* c) {
+  if (c->d_acc) return 0;
+  HIPCHK(c, hipMalloc(&c->d_acc, (size_t)c->N * 4 * sizeof(float)));
+  HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->N * 4 * sizeof(float), c->stream));
+  return 0;
+}
+
+// list -> sample -> commit -> observation, nothing in between that the host decides: the list's length stays on the
+// device, so the three launches after the list are sized for n_envs and return at once where their share is empty
+int sag_reset_device_async(sag_ctx* c, const uint8_t* d_mask, float* d_obs) {
+  if (!c) return SAG_ERR_ARG;
+  if (!c->have_tasks) return fail(c, SAG_ERR_STATE, "sag_reset_device_async before sag_set_tasks");
+  if (!c->have_layout) return fail(c, SAG_ERR_STATE, "sag_reset_device_async: a later episode needs an installed layout");
+  const bool doggo = c->cfg.robot == SAG_ROBOT_DOGGO;
+  if (doggo && (reinterpret_cast<uintptr_t>(d_obs) & 15)) return fail(c, SAG_ERR_ARG, "sag_reset_device_async: d_obs must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int N = c->N;
+  int32_t* counters = c->d_rstat + N;   // [0] listed envs, [1] failures of this call
+  HIPCHK(c, hipMemsetAsync(counters, 0, 2 * sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_reset_list, dim3((N + 255) / 256), dim3(256), 0, c->stream, d_mask, N, c->st_ids, counters);
+  ResetArgs a;
+  a.descs = c->d_descs; a.desc_of_env = c->d_desc_of_env; a.cfg = c->rcfg; a.S = c->S; a.I = c->I; a.N = N;
+  a.ids = c->st_ids; a.n = 0; a.n_dev = counters; a.robot = c->cfg.robot; a.first_episode = 0; a.have_state = 1;
+  a.episode0 = 0; a.env_id0 = c->env_id0;
+  a.k0 = (uint32_t)(c->cfg.seed & 0xffffffffu); a.k1 = (uint32_t)(c->cfg.seed >> 32);
+  a.rec_f = c->st_f; a.rec_i = c->st_i; a.status = c->d_rstat; a.n_fail = counters + 1;
+  hipLaunchKernelGGL(k_reset_sample, dim3(std::min((N + RS_BLOCK - 1) / RS_BLOCK, 5 * c->n_cu)), dim3(RS_BLOCK), 0, c->stream, a);
+  CommitArgs m;
+  m.S = c->S; m.I = c->I; m.N = N; m.ids = c->st_ids; m.n_dev = counters; m.rec_f = c->st_f; m.rec_i = c->st_i;
+  m.status = c->d_rstat; m.cost = c->d_cost; m.L_f = c->L_f; m.L_i = c->L_i;
+  m.hot = c->d_hot; m.hot_haz = c->d_hot ? c->d_hot + (size_t)N * HOT_FLOATS : nullptr;   // (the env's own record: hot_valid stays as it is)
+  m.acc = reinterpret_cast<float4*>(c->d_acc); m.totals = c->d_rtot;
+  hipLaunchKernelGGL(k_reset_commit, dim3((N + 255) / 256), dim3(256), 0, c->stream, m);
+  HIPCHK(c, hipGetLastError());
+  c->ext_pending = false;   // contact results were supplied for another state, and the host cannot know that the mask was empty
+  if (!d_obs) return SAG_OK;
+  if (doggo) {   // the whole batch into the context's own buffer, then the rows of the list
+    int rc = launch_step(c, nullptr, nullptr, nullptr, 0, 0, c->d_obs, nullptr, nullptr, nullptr, nullptr, nullptr, 1);
+    if (rc) return rc;
+    const int Q = c->rb.obs_dim / 4;
+    hipLaunchKernelGGL(k_copy_rows, dim3((unsigned)(((size_t)N * Q + 255) / 256)), dim3(256), 0, c->stream, c->st_ids, counters,
+                       c->d_rstat, Q, reinterpret_cast<const float4*>(c->d_obs), reinterpret_cast<float4*>(d_obs));
+    HIPCHK(c, hipGetLastError());
+    return SAG_OK;
+  }
+  StepArgs o;
+  o.S = c->S; o.I = c->I; o.N = N;
+  o.actions = nullptr; o.noise = nullptr; o.tape = nullptr; o.tape_len = 0;
+  o.nstep = 0; o.nstep_table = c->rb.nstep; o.h = (float)c->rb.dt; o.car = car_fric_constants(o.h);
+  o.key0 = a.k0; o.key1 = a.k1;
+  o.obs = d_obs; o.reward = nullptr; o.cost = nullptr; o.done = nullptr; o.goal_met = nullptr; o.tape_used = nullptr;
+  o.max_vases = c->cfg.max_vases; o.max_hazards = c->cfg.max_hazards; o.max_pillars = c->cfg.max_pillars;
+  o.max_buttons = c->cfg.max_buttons; o.has_box = c->cfg.has_box; o.G = c->G; o.observe_only = 1;
+  o.phase = c->phase; o.rows = nullptr; o.count = nullptr; o.DR = nullptr; o.dg_sched = nullptr; o.dg_phase = -1;
+  o.hot = nullptr; o.hot_haz = nullptr; o.ext_cc = nullptr; o.ext_btn = nullptr;
+  o.envs_per_wave = WAVE; o.busy_slots = 8 * c->n_cu; o.busy_kinds = 0; o.kind = nullptr; o.busy_total = nullptr;
+  const bool btn = c->cfg.max_buttons > 0, tbox = c->cfg.has_box != 0;
+  const dim3 grid((N + WAVE - 1) / WAVE);
+#define SAG_OBSERVE_ROWS(ROB, B_, X_) \
+  hipLaunchKernelGGL((k_observe_rows<ROB, B_, X_>), grid, dim3(WAVE), 0, c->stream, o, (const int32_t*)c->st_ids, (const int32_t*)counters, (const int32_t*)c->d_rstat)
+#define SAG_OBSERVE(ROB)                                \
+  do {                                                  \
+    if (!btn && !tbox) SAG_OBSERVE_ROWS(ROB, false, false); \
+    else if (btn && !tbox) SAG_OBSERVE_ROWS(ROB, true, false); \
+    else if (!btn && tbox) SAG_OBSERVE_ROWS(ROB, false, true); \
+    else SAG_OBSERVE_ROWS(ROB, true, true);             \
+  } while (0)
+  // (the context's own instantiation, as sag_observe runs it: the rows equal its rows bit for bit)
+  if (false) {}
+#if SAG_ONLY_ROBOT < 0 || SAG_ONLY_ROBOT == 0
+  else if (c->cfg.robot == SAG_ROBOT_POINT) SAG_OBSERVE(SAG_ROBOT_POINT);
+#endif
+#if SAG_ONLY_ROBOT < 0 || SAG_ONLY_ROBOT == 1
+  else if (c->cfg.robot == SAG_ROBOT_CAR) SAG_OBSERVE(SAG_ROBOT_CAR);
+#endif
+  else return fail(c, SAG_ERR_UNSUPPORTED, "this build holds the step kernels of robot %d only", SAG_ONLY_ROBOT);
+#undef SAG_OBSERVE
+#undef SAG_OBSERVE_ROWS
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+int sag_reset_device_counts(sag_ctx* c, int32_t clear, uint64_t* n_reset, uint64_t* n_failed) {
+  if (!c) return SAG_ERR_ARG;
+  unsigned long long tot[2] = {0, 0};
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (c->d_rtot) {
+    HIPCHK(c, hipMemcpyAsync(tot, c->d_rtot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+    if (clear) HIPCHK(c, hipMemsetAsync(c->d_rtot, 0, sizeof(tot), c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n_reset) *n_reset = tot[0];
+  if (n_failed) *n_failed = tot[1];
+  return SAG_OK;
+}
+
+int sag_episode_track_device(sag_ctx* c, const float* d_reward, const uint8_t* d_cost, const uint8_t* d_done, const uint8_t* d_goal_met,
+                             int32_t max_steps, uint8_t* d_ended, float* d_episode) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d_reward || !d_cost || !d_done || !d_goal_met || !d_ended || !d_episode || max_steps < 0)
+    return fail(c, SAG_ERR_ARG, "sag_episode_track_device: NULL buffer or negative max_steps");
+  if ((reinterpret_cast<uintptr_t>(d_reward) & 7) || (reinterpret_cast<uintptr_t>(d_episode) & 15))
+    return fail(c, SAG_ERR_ARG, "sag_episode_track_device: d_reward must be 8-byte and d_episode 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  int rc = ensure_acc(c);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_episode_track, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->N, d_reward, d_cost, d_done, d_goal_met,
+                     max_steps, reinterpret_cast<float4*>(c->d_acc), d_ended, reinterpret_cast<float4*>(d_episode));
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+int sag_episode_clear(sag_ctx* c, const uint8_t* d_mask) {
+  if (!c) return SAG_ERR_ARG;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const bool fresh = !c->d_acc;   // (then zeroed just now)
+  int rc = ensure_acc(c);
+  if (rc || fresh) return rc;
+  if (!d_mask) {
+    HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->N * 4 * sizeof(float), c->stream));
+    return SAG_OK;
+  }
+  hipLaunchKernelGGL(k_episode_clear, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->N, d_mask, reinterpret_cast<float4*>(c->d_acc));
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
 }
 
 int sag_step_device(sag_ctx* c, const float* d_actions, const float* d_noise, int32_t nstep, float* d_obs,

@@ -2387,11 +2387,9 @@ __global__ __launch_bounds__(WAVE, ROBOT == SAG_ROBOT_CAR ? SAG_CAR_BUSY_MIN_WAV
 #endif
 }
 
-// hot records of every env from the group-major state (after an install: all envs start busy)
-__global__ __launch_bounds__(256) void k_hot_refresh(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
-                                                      float* __restrict__ hot, float* __restrict__ hot_haz) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)N) return;
+// hot record of env i from the group-major state
+__device__ inline void hot_refresh_env(const float* __restrict__ S, const int32_t* __restrict__ I, int N, size_t i,
+                                       float* __restrict__ hot, float* __restrict__ hot_haz) {
   const float4* S4 = reinterpret_cast<const float4*>(S);
   float4* H = reinterpret_cast<float4*>(hot) + i * HOT_GROUPS;
   for (int g = 0; g < 5; g++) H[g] = S4[(size_t)g * N + i];
@@ -2403,17 +2401,19 @@ __global__ __launch_bounds__(256) void k_hot_refresh(const float* __restrict__ S
   for (int g = 0; g < 5; g++) Z[g] = S4[(size_t)(DG_HAZ + g) * N + i];
 }
 
+// hot records of every env (after an install: all envs start busy)
+__global__ __launch_bounds__(256) void k_hot_refresh(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
+                                                      float* __restrict__ hot, float* __restrict__ hot_haz) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (size_t)N) hot_refresh_env(S, I, N, i, hot, hot_haz);
+}
+
 // ---------------------------------------------------------------------------
 // record <-> SoA
 // ---------------------------------------------------------------------------
 // rec_f [n][SAG_REC_FLOATS], rec_i [n][SAG_REC_INTS] in device memory (AoS staging).
-__global__ void k_install(float* S, int32_t* I, int N, const int32_t* env_ids, int n,
-                          const float* rec_f, const int32_t* rec_i, int init_task) {
-  int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= n) return;
-  int i = env_ids ? env_ids[j] : j;
-  const float* rf = rec_f + (size_t)j * SAG_REC_FLOATS;
-  const int32_t* ri = rec_i + (size_t)j * SAG_REC_INTS;
+// one record (rf, ri) -> env i
+__device__ inline void install_env(float* S, int32_t* I, int N, int i, const float* rf, const int32_t* ri, int init_task) {
   for (int k = 0; k < SAG_REC_FLOATS; k++) S[saddr(k, (size_t)N, (size_t)i)] = rf[k];
   // derived word: which free bodies are awake = have a non-zero velocity component (SPECIFICATION, oracle world_forward
   // "sleeping bodies": a resting body takes part in a forward evaluation only once something active touches it), or are
@@ -2481,13 +2481,15 @@ __global__ void k_install(float* S, int32_t* I, int N, const int32_t* env_ids, i
   }
 }
 
-__global__ void k_extract(const float* S, const int32_t* I, int N, const int32_t* env_ids, int n,
-                          float* rec_f, int32_t* rec_i) {
+__global__ void k_install(float* S, int32_t* I, int N, const int32_t* env_ids, int n,
+                          const float* rec_f, const int32_t* rec_i, int init_task) {
   int j = blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
-  int i = env_ids ? env_ids[j] : j;
-  float* rf = rec_f + (size_t)j * SAG_REC_FLOATS;
-  int32_t* ri = rec_i + (size_t)j * SAG_REC_INTS;
+  install_env(S, I, N, env_ids ? env_ids[j] : j, rec_f + (size_t)j * SAG_REC_FLOATS, rec_i + (size_t)j * SAG_REC_INTS, init_task);
+}
+
+// env i -> one record (rf, ri)
+__device__ inline void extract_env(const float* S, const int32_t* I, int N, int i, float* rf, int32_t* ri) {
   for (int k = 0; k < SAG_REC_FLOATS; k++) rf[k] = S[saddr(k, (size_t)N, (size_t)i)];
   for (int k = 0; k < SAG_REC_INTS; k++) ri[k] = 0;
   unpack_meta((uint32_t)I[iaddr(DI_META, (size_t)N, (size_t)i)], ri);
@@ -2504,6 +2506,13 @@ __global__ void k_extract(const float* S, const int32_t* I, int N, const int32_t
     if (va[3] != 0 || va[4] != 0 || va[5] != 0) at_rest &= ~(1u << a);
   }
   ri[SAG_I_AWAKE] = (int32_t)at_rest;
+}
+
+__global__ void k_extract(const float* S, const int32_t* I, int N, const int32_t* env_ids, int n,
+                          float* rec_f, int32_t* rec_i) {
+  int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  extract_env(S, I, N, env_ids ? env_ids[j] : j, rec_f + (size_t)j * SAG_REC_FLOATS, rec_i + (size_t)j * SAG_REC_INTS);
 }
 
 // rows of an AoS record store by env id: dst[ids[j]] <- src[j] (scatter) or dst[j] <- src[ids[j]] (gather);

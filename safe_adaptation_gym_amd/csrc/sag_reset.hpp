@@ -45,6 +45,7 @@ struct ResetArgs {
   int32_t N;
   const int32_t* ids;           // envs to sample: ids[j], or j when nullptr
   int32_t n;
+  const int32_t* n_dev;         // the length of the list in device memory (stream-ordered form: the host never sees it), or nullptr: n
   int32_t robot, first_episode, have_state;
   uint32_t episode0;            // nonce of an env that has no layout yet
   int32_t env_id0;              // global id of env 0 of the context
@@ -225,14 +226,18 @@ __device__ inline void rs_write(const ResetArgs& p, const sag_task_desc& T, cons
   }
 }
 
-// One env per lane, one candidate per lane per loop trip (see the head of this file).  The grid strides over the list.
+// One env per lane, one candidate per lane per loop trip (see the head of this file).  The grid strides over the list,
+// whose length is p.n or, where the host never learns it, *p.n_dev (the grid is then sized for the upper bound).
 __global__ __launch_bounds__(RS_BLOCK) void k_reset_sample(ResetArgs p) {
 #pragma clang fp contract(off)
   __shared__ double sx[RS_MAX_ITEMS][RS_BLOCK], sy[RS_MAX_ITEMS][RS_BLOCK];
   const int lane = threadIdx.x;
   const int stride = gridDim.x * RS_BLOCK;
+  const int n = p.n_dev ? *p.n_dev : p.n;
   enum { PLACE = 0, GOAL = 1, NEXT = 2 };
-  int j = blockIdx.x * RS_BLOCK + lane - stride;   // the first NEXT moves to the lane's first env
+  // Entry j of the list goes to wavefront j mod gridDim: a list shorter than the grid (a few envs ending per step) gives
+  // every env a wavefront of its own, which then walks only that env's loops instead of the union over 64 envs' phases
+  int j = lane * gridDim.x + blockIdx.x - stride;   // the first NEXT moves to the lane's first env
   int phase = NEXT, i = 0, a = 0, k = 0, t = 0;
   uint32_t gid = 0, n4 = 0, nonce = 0;
   const sag_task_desc* T = nullptr;
@@ -254,7 +259,7 @@ __global__ __launch_bounds__(RS_BLOCK) void k_reset_sample(ResetArgs p) {
     if (!live) continue;
     if (phase == NEXT) {
       j += stride;
-      if (j >= p.n) { live = false; continue; }
+      if (j >= n) { live = false; continue; }
       i = p.ids ? p.ids[j] : j;
       gid = (uint32_t)(p.env_id0 + i);
       T = &p.descs[p.desc_of_env[i]];
@@ -314,14 +319,21 @@ __global__ __launch_bounds__(RS_BLOCK) void k_reset_sample(ResetArgs p) {
       sx[it.i_goal][lane] = x; sy[it.i_goal][lane] = y;
     }
     rs_write(p, *T, it, j, i, gid, nonce, sx, sy, lane);
+    p.status[i] = 0;   // (every listed env leaves with its status written: k_reset_commit reads it without a memset between calls)
     phase = NEXT;
   }
 }
 
-// masked envs -> a list of their indices (order of arrival; the records are keyed by env, not by position)
+// masked envs (nullptr: every env) -> a list of their indices (in any order; the records are keyed by env, not by position).  One atomic per
+// wavefront: the adds all hit one counter and serialise
 __global__ void k_reset_list(const uint8_t* mask, int N, int32_t* ids, int32_t* count) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N && mask[i]) ids[atomicAdd(count, 1)] = i;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x, lane = threadIdx.x & 63;
+  const bool on = i < N && (!mask || mask[i]);
+  const uint64_t m = __ballot(on);
+  int base = 0;
+  if (lane == 0 && m) base = atomicAdd(count, __popcll(m));
+  base = __shfl(base, 0);
+  if (on) ids[base + __popcll(m & ((1ull << lane) - 1))] = i;
 }
 
 // info['bound'] of every env from the installed state

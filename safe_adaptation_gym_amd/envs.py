@@ -52,7 +52,7 @@ class BatchedSafeAdaptationGym:
 
   def __init__(self, robot_base, n_envs=1, rgb_observation=False, config=None, devices=None,
                parity_rng=False, device_seed=None, render_lidars_and_collision=False, render_options=None,
-               device_buffers=False, device_reset=False):
+               device_buffers=False, device_reset=False, time_limit=None, auto_reset=False):
     # rgb_observation: the observation is the robot camera's 64 x 64 x 3 uint8 image
     # (safe_adaptation_gym.py:122-126,148-149), ray-cast on the device
     self._rgb_observation = bool(rgb_observation)
@@ -74,6 +74,20 @@ class BatchedSafeAdaptationGym:
     self.device_reset = bool(device_reset)
     if self.device_reset and self.parity_rng:
       raise ValueError('device_reset: parity_rng reproduces the reference\'s host MT19937 layout stream')
+    # time_limit / auto_reset: the episode loop on the contexts' streams (sag_episode_track_device after every step, then
+    # sag_reset_device_async of the envs that ended); see step()
+    self.time_limit = None if time_limit is None else int(time_limit)
+    self.auto_reset = bool(auto_reset)
+    self._track = self.time_limit is not None or self.auto_reset
+    if self._track:
+      if self.parity_rng:
+        raise ValueError('time_limit / auto_reset: parity_rng resets on the host, in the reference\'s order')
+      if not (self.device_buffers and self.device_reset):
+        raise ValueError('time_limit / auto_reset need device_buffers=True and device_reset=True')
+      if self._rgb_observation:
+        raise ValueError('time_limit / auto_reset with rgb_observation is not supported')
+      if self.time_limit is not None and self.time_limit <= 0:
+        raise ValueError(f'time_limit must be positive, not {time_limit}')
     self._last_obs = None   # device_reset, host buffers: what the last step() returned (rows kept by a masked reset)
     self._mask_bufs = None  # device_reset: per-shard device copies of a host reset mask
     self.devices = [0] if devices is None else list(devices)
@@ -154,24 +168,41 @@ class BatchedSafeAdaptationGym:
     self._task_ids = np.array([t.TASK_ID for t in self._tasks], np.int32)
     self._reward_dim = max(t.REWARD_DIM for t in self._tasks)
     self._persist = None  # task attributes that outlive an episode (filled by _pull_task_state)
+    if self._track:
+      self._map(lambda c, s, e: c.episode_clear())
     if self.device_reset:
       self._map(lambda c, s, e: c.set_tasks(self._descs, self._desc_of_env[s:e], self.base_config, env_id0=s))
       self._reset_device(first_episode=True)
     else:
       self._build_world(first_episode=True)
 
-  def reset(self, *, seed=None, return_info=False, options=None, mask=None):
+  def reset(self, *, seed=None, return_info=False, options=None, mask=None, sync=True):
     """mask (device_reset only): the envs to reset - a host bool / uint8 array [n_envs], or one device array of uint8
     [n_shard] per shard (a DeviceArray such as step()'s `done` view, or any __cuda_array_interface__ array on the shard's
     device; a list when there are several shards).  The other envs keep their state, and their rows of the returned
     observation are what the last step() returned.  A device mask written on another stream must be complete before
-    the call (as device actions)."""
+    the call (as device actions).
+
+    sync=False (device_reset and device_buffers): the same reset enqueued on the contexts' streams
+    (sag_reset_device_async) - the observation view comes back without waiting, the rows of the reset envs are written
+    by the stream; mask=None resets every env.  No ResamplingError is raised: an env whose layout cannot be sampled keeps
+    its state and observation row and gets bit 0 of its flags, and reset_counts() tells how many there were."""
     assert self._tasks is not None or (options is not None and 'task' in options), (
         'A task should be first set before reset.')
     if mask is not None and not self.device_reset:
       raise ValueError('reset(mask=...) needs device_reset=True')
     if mask is not None and options is not None and 'task' in options:
       raise ValueError('reset(mask=...) with a new task: a task is set for the whole batch')
+    ptrs = None
+    if not sync:
+      if not (self.device_buffers and self.device_reset):
+        raise ValueError('reset(sync=False) needs device_buffers=True and device_reset=True')
+      if self._rgb_observation or (options is not None and 'task' in options):
+        raise ValueError('reset(sync=False): not with rgb_observation or a new task')
+      if self._tasks is None:
+        raise ValueError('reset(sync=False): a task should be first set')
+    if mask is not None:
+      ptrs, hmask = self._mask_ptrs(mask)   # (checked before anything changes)
     self._episode += 1
     if seed is not None:
       self._base_seed = int(seed)
@@ -185,11 +216,28 @@ class BatchedSafeAdaptationGym:
     if options is not None and 'task' in options:
       self.set_task(options['task'])
       return self._observe()
+    if not sync:
+      bufs = self._dev_bufs()
+      for k, (c, b) in enumerate(zip(self._ctx, bufs)):
+        c.reset_device_async(None if ptrs is None else nat.C.c_void_p(ptrs[k]), b['obs'])
+      outs = [self._views(k)[0] for k in range(len(self._ctx))]
+      return outs[0] if len(outs) == 1 else outs
     if self.device_reset:
-      return self._reset_masked(mask) if mask is not None else (self._reset_device(first_episode=False), self._observe())[1]
+      if mask is not None:
+        return self._reset_masked(ptrs, hmask)
+      self._reset_device(first_episode=False)
+      if self._track:
+        self._map(lambda c, s, e: c.episode_clear())
+      return self._observe()
     self._pull_task_state()
     self._build_world(first_episode=False)
     return self._observe()
+
+  def reset_counts(self, clear=False):
+    """(envs reset, envs whose layout could not be sampled) by reset(sync=False) / auto_reset since the last clear,
+    summed over the shards.  Joins the streams."""
+    outs = [c.reset_counts(clear) for c in self._ctx]
+    return sum(o[0] for o in outs), sum(o[1] for o in outs)
 
   def step(self, action, sync=True):
     """-> (obs [N, obs_dim] f32, reward [N] (or [N, 2]) f32, done [N] bool,
@@ -201,7 +249,16 @@ class BatchedSafeAdaptationGym:
     anything with __cuda_array_interface__, e.g. a torch tensor on the GPU - of shape [N, nu] float32 (one per shard, in
     a list, when the batch is sharded over several `devices`; the results are then lists, one entry per shard).
     sync=False returns as soon as the launches are enqueued on the contexts' streams: call env.wait() before the
-    results are read on another stream.  The views are overwritten by the next step."""
+    results are read on another stream.  The views are overwritten by the next step.
+
+    time_limit=T: every step also runs the episode tracker on the stream.  `done` is then the `ended` byte - 0, 1
+    (terminated: the step's own done flag) or 2 (truncated: the episode reached T steps) -, info['terminated'] the step's
+    own done flags and info['episode'] a [N, 4] float32 device view: return, cost, length and goals met of each env's
+    last finished episode (rows of envs that have not finished one are zero).
+    auto_reset=True (time_limit=None: no limit): after the tracker the envs that ended are reset on the stream, and
+    their rows of the returned observation are the FIRST observation of the new episode; reward, cost and goal_met are
+    the final transition's.  The final observation of an ended episode is not kept: a learner that needs it steps
+    without auto_reset and calls reset(mask=done, sync=False) itself after reading it."""
     if self.device_buffers:
       return self._step_device(action, sync)
     a = np.asarray(action, np.float32).reshape(self.n_envs, self.robot.nu)
@@ -240,6 +297,10 @@ class BatchedSafeAdaptationGym:
         n = e - s
         b = {'act': c.dev_alloc(n * nu * 4), 'obs': c.dev_alloc(n * od * 4), 'rew': c.dev_alloc(n * 2 * 4),
              'cost': c.dev_alloc(n), 'done': c.dev_alloc(n), 'met': c.dev_alloc(n)}
+        if self._track:
+          b['ended'], b['episode'] = c.dev_alloc(n), c.dev_alloc(n * 16)
+          c.dev_upload(b['ended'], np.zeros(n, np.uint8))
+          c.dev_upload(b['episode'], np.zeros((n, 4), np.float32))
         if self._rgb_observation:
           b['img'] = c.dev_alloc(n * 64 * 64 * 3)
         self._dev.append(b)
@@ -280,12 +341,23 @@ class BatchedSafeAdaptationGym:
       c.step_device(d_act, None, -1, b['obs'], b['rew'], b['cost'], b['done'], b['met'])
       if self._rgb_observation:
         c.render_rgb_device(b['img'])
+      if self._track:
+        c.episode_track(b['rew'], b['cost'], b['done'], b['met'], self.time_limit or 0, b['ended'], b['episode'])
+        if self.auto_reset:
+          c.reset_device_async(b['ended'], b['obs'])
     if sync:
       self.wait()
     outs = [self._views(k) for k in range(len(self._ctx))]
     one = len(outs) == 1
     pick = (lambda j: outs[0][j]) if one else (lambda j: [o[j] for o in outs])
-    return pick(0), pick(1), pick(2), {'cost': pick(3), 'bound': self._bounds, 'goal_met': pick(4)}
+    info = {'cost': pick(3), 'bound': self._bounds, 'goal_met': pick(4)}
+    if not self._track:
+      return pick(0), pick(1), pick(2), info
+    A = nat.DeviceArray
+    ended = [A(c, b['ended'].value, (e - s,), np.uint8) for c, b, (s, e) in zip(self._ctx, bufs, self._ranges)]
+    episode = [A(c, b['episode'].value, (e - s, 4), np.float32) for c, b, (s, e) in zip(self._ctx, bufs, self._ranges)]
+    info.update(terminated=pick(2), episode=episode[0] if one else episode)
+    return pick(0), pick(1), ended[0] if one else ended, info
 
   def wait(self):
     """Joins the contexts' streams (after step(sync=False))."""
@@ -383,7 +455,9 @@ class BatchedSafeAdaptationGym:
       raise ResamplingError(f'Failed to generate layout for envs {bad[:8].tolist()}')
     self._bounds = np.concatenate([b for _, _, b in outs])
 
-  def _reset_masked(self, mask):
+  def _mask_ptrs(self, mask):
+    """-> (device pointer of every shard's mask bytes, the host mask as uint8 or None); ValueError for anything that is not
+    a mask, before anything is reset."""
     on_device = lambda x: isinstance(x, nat.DeviceArray) or hasattr(x, '__cuda_array_interface__')   # noqa: E731
     if isinstance(mask, (list, tuple)) and len(mask) == len(self._ctx) and all(on_device(x) for x in mask):
       dmasks = list(mask)
@@ -398,16 +472,21 @@ class BatchedSafeAdaptationGym:
         raise ValueError(f'mask: bool / uint8 of shape ({self.n_envs},), not {hmask.dtype} {hmask.shape}')
       hmask = hmask.astype(np.uint8)
     if dmasks is not None:
-      ptrs = [nat.device_pointer(m, (e - s,), c.device, np.uint8) for c, (s, e), m in zip(self._ctx, self._ranges, dmasks)]
-    else:   # a host mask travels in a buffer of each shard
-      if self._mask_bufs is None:
-        self._mask_bufs = [c.dev_alloc(e - s) for c, (s, e) in zip(self._ctx, self._ranges)]
-      for c, (s, e), buf in zip(self._ctx, self._ranges, self._mask_bufs):
-        c.dev_upload(buf, hmask[s:e])
-      ptrs = [buf.value for buf in self._mask_bufs]
+      return [nat.device_pointer(m, (e - s,), c.device, np.uint8) for c, (s, e), m in zip(self._ctx, self._ranges, dmasks)], None
+    # a host mask travels in a buffer of each shard
+    if self._mask_bufs is None:
+      self._mask_bufs = [c.dev_alloc(e - s) for c, (s, e) in zip(self._ctx, self._ranges)]
+    for c, (s, e), buf in zip(self._ctx, self._ranges, self._mask_bufs):
+      c.dev_upload(buf, hmask[s:e])
+    return [buf.value for buf in self._mask_bufs], hmask
+
+  def _reset_masked(self, ptrs, hmask):
     self._reset_device(first_episode=False, masks=[nat.C.c_void_p(p) for p in ptrs])
+    if self._track:
+      for c, p in zip(self._ctx, ptrs):
+        c.episode_clear(nat.C.c_void_p(p))
     # the observation: rows of reset envs are formed at their new state, the others are what the last step returned
-    if dmasks is None:
+    if hmask is not None:
       rows = [hmask[s:e].astype(bool) for s, e in self._ranges]
     else:
       rows = [c.dev_download(nat.C.c_void_p(p), (e - s,), np.uint8).astype(bool) for c, (s, e), p in zip(self._ctx, self._ranges, ptrs)]
