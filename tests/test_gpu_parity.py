@@ -8,6 +8,7 @@ import pytest
 
 import batch_util as bu
 import golden_util as gu
+import render_ref as rr
 from oracle_lib import Oracle
 
 pytestmark = pytest.mark.gpu
@@ -1442,7 +1443,8 @@ def test_parity_rng_mode_matches_reference_draw_order(nat, oracle):
 def test_rgb_observation_matches_oracle(nat, oracle, robot, task):
   """Every pixel is a hard decision (surface hit, checker square, 8-bit rounding) evaluated in fp64
   on both sides: images agree exactly except where libm differences flip a decision - bounded to
-  0.1 % of the pixels, never by more than the two candidate colours of an edge."""
+  0.1 % of the pixels, and every differing pixel is one that the independent reference (tests/render_ref.py)
+  leaves open and shows one of its candidate colours."""
   n = 24
   rid = {'point': 0, 'car': 1, 'doggo': 2}[robot]
   rf, ri = bu.sample_records_native(robot, task, n, seed=31)
@@ -1457,6 +1459,7 @@ def test_rgb_observation_matches_oracle(nat, oracle, robot, task):
     diff = (img.astype(int) - ref.astype(int))
     bad = np.abs(diff).max(-1) > 0
     assert bad.mean() <= 1e-3, f'{bad.sum()} pixels differ'
+    rr.differing_pixels(oracle, img, ref, rf, ri, rid, 0, 64, 64, what=f'test_rgb_observation_matches_oracle[{robot}-{task}] round {rounds}')
     assert len(np.unique(img.reshape(-1, 3), axis=0)) > 20          # not a flat image
     assert (img[:, :8].astype(int).mean() != img[:, -8:].astype(int).mean())
     for _ in range(5):   # move, then render again
@@ -1494,6 +1497,8 @@ def test_human_view_matches_oracle(nat, oracle, robot, task, camera):
     ref = np.stack([oracle.render(oracle.env(rf2[k], ri2[k]), rid, cam, W, H, True, obs[k, :48], cost[k]) for k in range(n)])
     bad = np.abs(img.astype(int) - ref.astype(int)).max(-1) > 0
     assert bad.mean() <= 1e-3, f'{bad.sum()} pixels differ'
+    rr.differing_pixels(oracle, img, ref, rf2, ri2, rid, cam, W, H, True, obs, cost,
+                        what=f'test_human_view_matches_oracle[{robot}-{task}-{camera}] round {rounds}')
     plain = ctx.render(camera, W, H, overlays=False)
     if camera != 'vision':   # (the rings float above the robot's own camera, out of its view)
       assert (plain != img).any(), 'the overlays must be visible'

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import batch_util as bu
+import render_ref as rr
 import reset_sampler_ref as R
 from test_device_reset import KEY, _assert_records, _cfg, _prev, _ref_batch
 
@@ -645,7 +646,8 @@ def test_env_api_masked_reset_cycles(nat, oracle, robot, device_buffers):
 @pytest.mark.gpu
 def test_env_api_masked_reset_with_rgb_observation(nat, oracle):
   """rgb_observation with masked resets (doggo / haul_box, 24 envs): the returned images are the oracle's render of
-  get_state() within the pixel budget of test_rgb_observation_matches_oracle (0.1 % of the pixels)."""
+  get_state() within the pixel budget of test_rgb_observation_matches_oracle (0.1 % of the pixels), and every differing pixel is
+  one that the independent reference (tests/render_ref.py) leaves open."""
   n = 24
   env = _make_env('doggo', 'haul_box', n_envs=n, seed=31, rgb_observation=True)
   env.reset()
@@ -664,6 +666,7 @@ def test_env_api_masked_reset_with_rgb_observation(nat, oracle):
     bad = np.abs(img.astype(int) - ref.astype(int)).max(-1) > 0
     assert bad.mean() <= 1e-3, f'{bad.sum()} pixels differ'
     assert bad[m].mean() <= 1e-3, f'{bad[m].sum()} pixels of the reset envs differ'
+    rr.differing_pixels(oracle, img, ref, f, i, 2, 0, 64, 64, what=f'test_env_api_masked_reset_with_rgb_observation cycle {cycle}')
   env.close()
 
 
