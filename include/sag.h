@@ -376,7 +376,9 @@ int sag_set_tasks(sag_ctx* ctx, const sag_task_desc* descs, int32_t n_descs, con
  *                 0: SAG_F_CTRL_SCALE, SAG_F_BOUND, SAG_I_BTN_STATE, SAG_I_CATCH_TIMER and SAG_F_CATCH + 2, + 3 are kept
  *                 from the env's current state (needs an installed layout)
  *   episode0      the episode nonce of envs of a context that has no layout yet; otherwise each reset env's nonce
- *                 advances by one (as sag_reset), so an env never draws the same layout twice under one key
+ *                 advances by one (as sag_reset), so an env never draws the same layout twice under one key.  A later
+ *                 episode draws under the SAG_I_ENV_ID the env carries: env_id0 + i, unless sag_fork_device with
+ *                 SAG_FORK_SAME_STREAM gave it its source's
  *   d_mask        [n_envs] DEVICE bytes: only envs with a non-zero byte are reset; NULL: every env.  A mask written on
  *                 another stream must be complete before the call.
  *   status        [n_envs] host, may be NULL: 0, -1 (layout attempts exhausted), -2 (goal resample exhausted); 0 for envs
@@ -418,6 +420,31 @@ int sag_episode_track_device(sag_ctx* ctx, const float* d_reward, const uint8_t*
                              const uint8_t* d_goal_met, int32_t max_steps, uint8_t* d_ended, float* d_episode);
 /* Zero the accumulators of the masked envs (NULL: all), stream-ordered. */
 int sag_episode_clear(sag_ctx* ctx, const uint8_t* d_mask);
+
+/* ---- fork on the device (throughput mode) -------------------------------------------------------
+ * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`
+ * itself (a fork inside a batch) or another one, of any n_envs (a few real envs feeding many planner envs; a second context
+ * of the same size is a snapshot: fork into it to save, fork back to restore).  Enqueued on dst's stream, returns without
+ * waiting, no host copy.  Between two contexts dst's stream first waits for what is enqueued on src's (a step, say), and
+ * src's stream then waits for the copy, so a following step of src cannot overtake it.
+ *   d_src   [dst n_envs] DEVICE int32, complete before the call (as a reset mask).  d_src[i] < 0: env i is left alone.
+ * Commit is per env.  Rejected - the env keeps everything - are an index >= src's n_envs and, in one context, a source that
+ * this call overwrites: with j = d_src[i] != i, env i is rejected if d_src[j] >= 0 && d_src[j] != j (d_src[i] == i is a
+ * harmless copy onto itself), so no read of the call meets one of its writes.
+ * A committed env receives the record (every field of sag_get_state, its step, nonce and flags included) except
+ * SAG_I_ENV_ID, the source's row of the layout store (sag_reset restarts the source's layout), its episode accumulators
+ * (zero if only dst tracks episodes), its cost byte and, when both contexts have tasks, its task descriptor index.  Its next
+ * step runs as after sag_set_state.  It keeps its own SAG_I_ENV_ID, in the state and in the layout store: its action noise
+ * and in-step draws differ from the source's from the next step on.  With SAG_FORK_SAME_STREAM the env id is copied too:
+ * source and copy draw the same numbers (common random numbers for a planner) and sample the same next layout.
+ * Pending external contacts (sag_set_ext_contacts) of dst are dropped.  No timing events are recorded.
+ * SAG_ERR_ARG, with nothing enqueued: NULL d_src, unknown flag bits, another robot, other capacities (max_*, has_box),
+ * another device, or both contexts with tasks whose descriptor tables differ.  SAG_ERR_STATE: a context without a layout,
+ * or dst with tasks and src without. */
+enum sag_fork_flags { SAG_FORK_SAME_STREAM = 1 };
+int sag_fork_device(sag_ctx* dst, sag_ctx* src, const int32_t* d_src, int32_t flags);
+/* Envs copied / envs rejected by sag_fork_device into ctx since the last call with clear != 0.  Synchronises the stream. */
+int sag_fork_counts(sag_ctx* ctx, int32_t clear, uint64_t* n_copied, uint64_t* n_rejected);
 
 #ifdef __cplusplus
 }

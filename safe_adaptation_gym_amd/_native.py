@@ -26,6 +26,7 @@ F_BOUND = 141
  I_CATCH_TIMER, I_ACTIVE_MASK, I_STEP, I_ENV_ID, I_FLAGS, I_EPISODE, I_AWAKE) = range(16)
 
 ROBOT_IDS = {'point': 0, 'car': 1, 'doggo': 2}
+FORK_SAME_STREAM = 1   # enum sag_fork_flags
 
 EXPORTS = [
     'sag_robot_info', 'sag_create', 'sag_destroy', 'sag_last_error', 'sag_set_layout',
@@ -34,7 +35,7 @@ EXPORTS = [
     'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_debug_doggo_coop',
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
-    'sag_episode_clear'
+    'sag_episode_clear', 'sag_fork_device', 'sag_fork_counts'
 ]
 
 
@@ -113,6 +114,8 @@ def load():
   lib.sag_reset_device_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
   lib.sag_episode_track_device.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp]
   lib.sag_episode_clear.argtypes = [vp, vp]
+  lib.sag_fork_device.argtypes = [vp, vp, vp, C.c_int32]
+  lib.sag_fork_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
   _lib = lib
   return lib
 
@@ -459,6 +462,21 @@ class Context:
 
   def episode_clear(self, d_mask=None):
     self._check(self.lib.sag_episode_clear(self.h, d_mask), 'sag_episode_clear')
+
+  def fork_device(self, d_src, source=None, same_stream=False, flags=None):
+    """sag_fork_device: env i takes the complete state of env d_src[i] of `source` (a Context on the same device; default:
+    this one), enqueued on this context's stream - no wait, no host copy.  d_src: device pointer of [n_envs] int32,
+    negative = keep.  Rejections (an index past the source's envs, a source that the call overwrites) are data:
+    fork_counts().  same_stream: the env id is copied too (SAG_FORK_SAME_STREAM); `flags` overrides the flag word."""
+    if flags is None:
+      flags = FORK_SAME_STREAM if same_stream else 0
+    self._check(self.lib.sag_fork_device(self.h, (self if source is None else source).h, d_src, int(flags)), 'sag_fork_device')
+
+  def fork_counts(self, clear=False):
+    """(envs copied, envs rejected) by fork_device into this context since the last clear; joins the stream."""
+    a, b = C.c_uint64(), C.c_uint64()
+    self._check(self.lib.sag_fork_counts(self.h, int(bool(clear)), C.byref(a), C.byref(b)), 'sag_fork_counts')
+    return a.value, b.value
 
   def set_seed(self, seed):
     """Key of the device-side generator of throughput mode (env.seed())."""

@@ -21,6 +21,7 @@
 #include "sag_device.hpp"
 #include "sag_reset.hpp"
 #include "sag_rollout.hpp"
+#include "sag_fork.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -104,6 +105,11 @@ struct sag_ctx {
   float* d_rbound = nullptr;    // [N]
   unsigned long long* d_rtot = nullptr;   // sag_reset_device_async: envs reset, envs whose sampling failed (sag_reset_device_counts)
   float* d_acc = nullptr;       // [N] float4 episode accumulators (sag_episode_track_device), allocated on first use
+  // sag_fork_device: the descriptor table as given to sag_set_tasks (two contexts fork only under the same table), the
+  // counters (envs copied, envs rejected) and the events that order a fork between two contexts' streams
+  std::vector<sag_task_desc> h_descs;
+  unsigned long long* d_ftot = nullptr;
+  hipEvent_t ev_xsrc = nullptr, ev_xdone = nullptr;
   std::string err;
 };
 
@@ -503,6 +509,8 @@ int sag_create(const sag_config* cfg, sag_ctx** out) {
   }
   CREATE_CHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
   CREATE_CHK(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  CREATE_CHK(hipEventCreateWithFlags(&c->ev_xsrc, hipEventDisableTiming));
+  CREATE_CHK(hipEventCreateWithFlags(&c->ev_xdone, hipEventDisableTiming));
   if (const char* e = getenv("SAG_EARLY_FORK")) c->early_fork = atoi(e);
   if (const char* e = getenv("SAG_BUSY_KINDS")) c->busy_kinds = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("SAG_BUSY_KINDS_MIN")) c->kinds_min = atoi(e);
@@ -561,12 +569,14 @@ int sag_destroy(sag_ctx* c) {
   for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   void* bufs[] = {c->S, c->I, c->G, c->d_rows, c->d_count, c->d_kind, c->L_f, c->L_i, c->st_f, c->st_i, c->st_ids, c->d_act, c->d_noise,
                   c->d_tape, c->d_obs, c->d_rew, c->d_cost, c->d_done, c->d_met, c->d_used, c->scratch, c->d_rgb, c->d_dr, c->d_dg_sched, c->d_hot,
-                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc};
+                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
   if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
   if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+  if (c->ev_xsrc) (void)hipEventDestroy(c->ev_xsrc);
+  if (c->ev_xdone) (void)hipEventDestroy(c->ev_xdone);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return SAG_OK;
@@ -724,6 +734,7 @@ int sag_set_tasks(sag_ctx* c, const sag_task_desc* descs, int32_t n_descs, const
   HIPCHK(c, hipMemcpyAsync(c->d_desc_of_env, desc_of_env, (size_t)c->N * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));   // the host arrays are the caller's
   c->rcfg = *cfg; c->env_id0 = env_id0;
+  c->h_descs.assign(descs, descs + n_descs);
   c->have_tasks = true;
   return SAG_OK;
 }
@@ -919,6 +930,73 @@ int sag_episode_clear(sag_ctx* c, const uint8_t* d_mask) {
   }
   hipLaunchKernelGGL(k_episode_clear, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->N, d_mask, reinterpret_cast<float4*>(c->d_acc));
   HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+// decide -> state -> layout rows -> int words and what hangs on an env, on dst's stream.  Between two contexts the source's
+// stream is joined first (what is enqueued there, a step for one, is seen) and waits for the copy afterwards (its next step
+// cannot overtake the reads).
+int sag_fork_device(sag_ctx* c, sag_ctx* s, const int32_t* d_src, int32_t flags) {
+  if (!c) return SAG_ERR_ARG;
+  if (!s) return fail(c, SAG_ERR_ARG, "sag_fork_device: the source context is NULL");
+  if (!d_src) return fail(c, SAG_ERR_ARG, "sag_fork_device: d_src is NULL");
+  if (flags & ~SAG_FORK_SAME_STREAM) return fail(c, SAG_ERR_ARG, "sag_fork_device: unknown flag bits 0x%x", flags & ~SAG_FORK_SAME_STREAM);
+  if (s->cfg.robot != c->cfg.robot) return fail(c, SAG_ERR_ARG, "sag_fork_device: robot %d into robot %d", s->cfg.robot, c->cfg.robot);
+  if (s->cfg.device != c->cfg.device) return fail(c, SAG_ERR_ARG, "sag_fork_device: device %d into device %d", s->cfg.device, c->cfg.device);
+  if (s->cfg.max_hazards != c->cfg.max_hazards || s->cfg.max_vases != c->cfg.max_vases || s->cfg.max_pillars != c->cfg.max_pillars ||
+      s->cfg.max_buttons != c->cfg.max_buttons || (s->cfg.has_box != 0) != (c->cfg.has_box != 0))
+    return fail(c, SAG_ERR_ARG, "sag_fork_device: the contexts' capacities differ");
+  if (!s->have_layout || !c->have_layout) return fail(c, SAG_ERR_STATE, "sag_fork_device before sag_set_layout");
+  if (c->have_tasks && !s->have_tasks)
+    return fail(c, SAG_ERR_STATE, "sag_fork_device: the destination has tasks and the source none (a later device reset would sample for the wrong task)");
+  const bool tasks = c->have_tasks && s->have_tasks;
+  if (tasks && s != c && (s->h_descs.size() != c->h_descs.size() ||
+                          memcmp(s->h_descs.data(), c->h_descs.data(), c->h_descs.size() * sizeof(sag_task_desc)) != 0))
+    return fail(c, SAG_ERR_ARG, "sag_fork_device: the contexts' task descriptor tables differ");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (!c->d_ftot) {
+    HIPCHK(c, hipMalloc(&c->d_ftot, 2 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMemsetAsync(c->d_ftot, 0, 2 * sizeof(unsigned long long), c->stream));
+  }
+  if (s != c) {
+    HIPCHK(c, hipEventRecord(s->ev_xsrc, s->stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, s->ev_xsrc, 0));
+  }
+  ForkArgs p;
+  p.S = c->S; p.I = c->I; p.N = c->N; p.src_S = s->S; p.src_I = s->I; p.src_N = s->N;
+  p.src = d_src; p.from = c->st_ids; p.same_stream = (flags & SAG_FORK_SAME_STREAM) != 0;
+  p.L_f = c->L_f; p.L_i = c->L_i; p.src_L_f = s->L_f; p.src_L_i = s->L_i;
+  p.acc = reinterpret_cast<float4*>(c->d_acc); p.src_acc = reinterpret_cast<const float4*>(s->d_acc);
+  p.cost = c->d_cost; p.src_cost = s->d_cost;
+  p.desc_of_env = tasks ? c->d_desc_of_env : nullptr; p.src_desc_of_env = tasks ? s->d_desc_of_env : nullptr;
+  p.hot = c->d_hot; p.hot_haz = c->d_hot ? c->d_hot + (size_t)c->N * HOT_FLOATS : nullptr;   // (the env's own record: hot_valid stays as it is)
+  p.totals = c->d_ftot;
+  const unsigned blocks = (unsigned)((c->N + 255) / 256);
+  const size_t pieces = (size_t)c->N * FORK_ROW_PIECES;
+  hipLaunchKernelGGL(k_fork_decide, dim3(blocks), dim3(256), 0, c->stream, p);
+  hipLaunchKernelGGL(k_fork_state, dim3(blocks * FORK_CHUNKS), dim3(256), 0, c->stream, p);
+  hipLaunchKernelGGL(k_fork_rows, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, c->stream, p);
+  hipLaunchKernelGGL(k_fork_finish, dim3(blocks), dim3(256), 0, c->stream, p);
+  HIPCHK(c, hipGetLastError());
+  c->ext_pending = false;   // contact results were supplied for another state
+  if (s != c) {
+    HIPCHK(c, hipEventRecord(c->ev_xdone, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(s->stream, c->ev_xdone, 0));
+  }
+  return SAG_OK;
+}
+
+int sag_fork_counts(sag_ctx* c, int32_t clear, uint64_t* n_copied, uint64_t* n_rejected) {
+  if (!c) return SAG_ERR_ARG;
+  unsigned long long tot[2] = {0, 0};
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (c->d_ftot) {
+    HIPCHK(c, hipMemcpyAsync(tot, c->d_ftot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+    if (clear) HIPCHK(c, hipMemsetAsync(c->d_ftot, 0, sizeof(tot), c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (n_copied) *n_copied = tot[0];
+  if (n_rejected) *n_rejected = tot[1];
   return SAG_OK;
 }
 

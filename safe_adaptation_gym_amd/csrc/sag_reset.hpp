@@ -261,7 +261,9 @@ __global__ __launch_bounds__(RS_BLOCK) void k_reset_sample(ResetArgs p) {
       j += stride;
       if (j >= n) { live = false; continue; }
       i = p.ids ? p.ids[j] : j;
-      gid = (uint32_t)(p.env_id0 + i);
+      // a later episode draws under the id the env carries: its own (env_id0 + i) unless a fork with SAG_FORK_SAME_STREAM gave
+      // it its source's, in which case source and copy go on sampling the same layouts
+      gid = p.have_state && !p.first_episode ? (uint32_t)p.I[iaddr(DI_ENVID, (size_t)p.N, (size_t)i)] : (uint32_t)(p.env_id0 + i);
       T = &p.descs[p.desc_of_env[i]];
       it = rs_items(*T, p.cfg);
       margin = p.cfg.placements_margin + (p.robot == SAG_ROBOT_DOGGO ? 0.165 : 0.0);

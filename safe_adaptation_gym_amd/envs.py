@@ -90,6 +90,7 @@ class BatchedSafeAdaptationGym:
         raise ValueError(f'time_limit must be positive, not {time_limit}')
     self._last_obs = None   # device_reset, host buffers: what the last step() returned (rows kept by a masked reset)
     self._mask_bufs = None  # device_reset: per-shard device copies of a host reset mask
+    self._fork_bufs = None  # fork(): per-shard device copies of a host source-index array
     self.devices = [0] if devices is None else list(devices)
     if self.n_envs < len(self.devices):
       self.devices = self.devices[:self.n_envs]
@@ -237,6 +238,108 @@ class BatchedSafeAdaptationGym:
     """(envs reset, envs whose layout could not be sampled) by reset(sync=False) / auto_reset since the last clear,
     summed over the shards.  Joins the streams."""
     outs = [c.reset_counts(clear) for c in self._ctx]
+    return sum(o[0] for o in outs), sum(o[1] for o in outs)
+
+  def fork(self, src, same_stream=False, source=None):
+    """Env i takes the complete state of env src[i] of `source` (default: this env) on the device (sag_fork_device): no
+    record leaves the GPU.  For shooting planners (every real env broadcast to K candidates), evaluation of many action
+    sequences from one state, rewinding to a saved state (fork into a second env of the same size, fork back) and cloning
+    the best members of a population.  Needs device_reset=True (throughput mode).
+
+    src: an int array [n_envs] of global env indices into `source`, negative = keep the env as it is; or, already on the
+    device, one int32 array [n_shard] per shard with shard-LOCAL indices (a DeviceArray or any __cuda_array_interface__
+    array on the shard's device; a list when there are several shards).  A host src is checked before anything is
+    launched - ValueError for a wrong shape or dtype, an index out of range, a source that the same call overwrites
+    (src[src[i]] must be negative or src[i] itself) and a source on another shard than its destination.  A device src is
+    downloaded once (4 B per env and a join of the stream) so that the host mirrors follow; there the device rejects what
+    a host src would raise for, env by env: fork_counts().
+    source: another env of the same robot, devices, task descriptors and world config; shard k forks from its shard k.
+    same_stream: the copy also takes the source's env id, so both draw the same action noise and in-step numbers from
+    the next step on and sample the same next layout (common random numbers); otherwise a copy keeps its own stream.
+
+    info['bound'], the task mirrors and, with host buffers, the last observation row follow the fork.  With
+    device_buffers=True the call does not wait (the next wait() or synchronous step joins it), and the views returned by
+    the last step() are not touched: a caller that needs the copies' rows gathers them itself (obs[src]); the next step
+    writes them anyway."""
+    if not self.device_reset or self.parity_rng:
+      raise ValueError('fork() needs device_reset=True (throughput mode)')
+    other = self if source is None else source
+    if other is not self:
+      if not isinstance(other, BatchedSafeAdaptationGym) or not other.device_reset or other.parity_rng:
+        raise ValueError('fork(source=...): an env made with device_reset=True')
+      if other.robot.name != self.robot.name or other.devices != self.devices:
+        raise ValueError('fork(source=...): another robot or other devices')
+    if self._tasks is None or other._tasks is None:
+      raise ValueError('fork(): a task should be first set (in both envs)')
+    if other is not self and (other._descs != self._descs or
+                              bytes(nat.world_config(other.base_config)) != bytes(nat.world_config(self.base_config))):
+      raise ValueError('fork(source=...): the envs differ in their task descriptors or world config')
+    on_device = lambda x: isinstance(x, nat.DeviceArray) or hasattr(x, '__cuda_array_interface__')   # noqa: E731
+    dsrc = None
+    if isinstance(src, (list, tuple)) and len(src) == len(self._ctx) and all(on_device(x) for x in src):
+      dsrc = list(src)
+    elif on_device(src):
+      if len(self._ctx) != 1:
+        raise ValueError(f'{len(self._ctx)} shards: pass one device src per shard')
+      dsrc = [src]
+    if dsrc is not None:
+      ptrs = [nat.device_pointer(x, (e - s,), c.device, np.int32) for c, (s, e), x in zip(self._ctx, self._ranges, dsrc)]
+      local = [c.dev_download(nat.C.c_void_p(p), (e - s,), np.int32) for c, (s, e), p in zip(self._ctx, self._ranges, ptrs)]
+    else:
+      h = np.asarray(src)
+      if h.shape != (self.n_envs,) or h.dtype.kind not in 'iu':
+        raise ValueError(f'src: integers of shape ({self.n_envs},), not {h.dtype} {h.shape}')
+      h = h.astype(np.int64)
+      if (h >= other.n_envs).any():
+        raise ValueError(f'src: index {int(h.max())} out of range ({other.n_envs} envs in the source)')
+      local = []
+      for (s, e), (ss, se) in zip(self._ranges, other._ranges):
+        part = h[s:e]
+        if ((part >= 0) & ((part < ss) | (part >= se))).any():
+          raise ValueError('src: a source on another shard than its destination')
+        local.append(np.where(part < 0, -1, part - ss).astype(np.int32))
+    # the commit rule of the device (include/sag.h), per shard
+    commit = []
+    for k, loc in enumerate(local):
+      n_src = other._ranges[k][1] - other._ranges[k][0]
+      ok = (loc >= 0) & (loc < n_src)
+      if other is self:
+        j = np.where(ok, loc, 0)
+        jj = loc[j]
+        ok &= (j == np.arange(len(loc))) | (jj < 0) | (jj == j)
+      if dsrc is None and (ok != (loc >= 0)).any():
+        raise ValueError('src: a source env is itself overwritten by this call')
+      commit.append(ok)
+    if dsrc is None:
+      if self._fork_bufs is None:
+        self._fork_bufs = [c.dev_alloc(4 * (e - s)) for c, (s, e) in zip(self._ctx, self._ranges)]
+      for c, buf, loc in zip(self._ctx, self._fork_bufs, local):
+        c.dev_upload(buf, loc)
+      ptrs = [buf.value for buf in self._fork_bufs]
+    for c, oc, p in zip(self._ctx, other._ctx, ptrs):
+      c.fork_device(nat.C.c_void_p(p), oc, same_stream=same_stream)
+    # host mirrors
+    dst = np.concatenate([np.flatnonzero(ok) + s for ok, (s, e) in zip(commit, self._ranges)])
+    frm = np.concatenate([loc[ok].astype(np.int64) + ss for loc, ok, (ss, se) in zip(local, commit, other._ranges)])
+    if dst.size:
+      self._bounds = self._bounds.copy()
+      self._bounds[dst] = other._bounds[frm]
+      tasks = list(self._tasks)
+      for i, j in zip(dst.tolist(), frm.tolist()):
+        tasks[i] = other._tasks[j]
+      self._tasks = tasks
+      self._task_ids[dst] = other._task_ids[frm]
+      self._desc_of_env[dst] = other._desc_of_env[frm]
+      self._reward_dim = max(t.REWARD_DIM for t in self._tasks)
+      if self._last_obs is not None and other._last_obs is not None:
+        rows = other._last_obs[frm]
+        self._last_obs[dst] = rows
+    if not self.device_buffers:
+      self.wait()
+
+  def fork_counts(self, clear=False):
+    """(envs copied, envs rejected) by fork() since the last clear, summed over the shards.  Joins the streams."""
+    outs = [c.fork_counts(clear) for c in self._ctx]
     return sum(o[0] for o in outs), sum(o[1] for o in outs)
 
   def step(self, action, sync=True):
@@ -387,6 +490,9 @@ class BatchedSafeAdaptationGym:
     for c, p in zip(self._ctx, self._mask_bufs or []):
       c.dev_free(p)
     self._mask_bufs = None
+    for c, p in zip(self._ctx, self._fork_bufs or []):
+      c.dev_free(p)
+    self._fork_bufs = None
     for c in self._ctx:
       c.close()
     if self._pool:
