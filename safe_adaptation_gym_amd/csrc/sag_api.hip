@@ -362,9 +362,9 @@ int launch_step(sag_ctx* c, const float* d_act, const float* d_noise, const uint
   // at once (measured at 4 M envs: +8 % throughput, tools/ab.sh run).
   size_t quiet_lds_extra = 0;
   if (split) {
-    const int quiet_own = (LS_YAW + (c->cfg.robot == SAG_ROBOT_CAR ? 25 : 17)) * WAVE * (int)sizeof(float);
-    const int busy_own = LDS_FLOATS * (int)sizeof(float) + WAVE * (int)sizeof(int);
-    quiet_lds_extra = busy_own > quiet_own ? (busy_own - quiet_own + 511) / 512 * 512 : 0;
+    // (the static array differs between the instances of a robot - quiet_lds_rows -, the sum does not)
+    const int quiet_own = quiet_lds_rows(c->cfg.robot, btn, tbox) * WAVE * (int)sizeof(float);
+    quiet_lds_extra = (size_t)(quiet_lds_total(c->cfg.robot) - quiet_own);
   }
 #define SAG_LAUNCH3(ROB, B_, X_)                                                                         \
   do {                                                                                                  \

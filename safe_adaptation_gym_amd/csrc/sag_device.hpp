@@ -639,8 +639,9 @@ __device__ inline int collide_list(BV& A, float ca, float sa, BV& B, int shB, fl
 //         33..50 a pool of DPOOL dynamic entries (vx vy w ax ay aw), handed to the bodies that
 //                move or get touched during the step; further ones spill to global memory
 // = 13 KB per wavefront -> 12 wavefronts per CU.  For the observation the region from slot 22
-// on is reused as a [lane][17] staging tile per 16-column chunk, read back transposed so the
-// row-major [N][60] output is written in 64-B runs instead of scattered dwords.
+// on is reused as a staging tile per 16-column chunk, read back transposed so the row-major
+// [N][60] output is written in 64-B runs instead of scattered dwords; the instance without
+// buttons and task object stages its whole row at once, over the x / y slots too (obs_whole_rows).
 constexpr int NBODY = SAG_MAX_VASES + 1, BOX_ID = SAG_MAX_VASES;
 constexpr int DPOOL = 3;
 enum { LS_X = 0, LS_Y = NBODY, LS_YAW = 2 * NBODY, LS_POOL = 3 * NBODY };
@@ -815,8 +816,9 @@ __device__ inline float angle_bins(float ex, float ey) {
   return t;
 }
 
+// tile_base: where the chunk's [bin][lane] tile starts in lds (floats)
 __device__ inline void lidar_point(float* lds, int lane, float rxf, float ryf, float yawf, float cf, float sf,
-                                   float px, float py) {
+                                   float px, float py, const int tile_base = STG_BASE) {
   const float w0 = px - rxf, w1 = py - ryf;
   const float ex = __builtin_fmaf(w0, cf, w1 * sf), ey = __builtin_fmaf(w1, cf, -(w0 * sf));
   const float dist = __builtin_amdgcn_sqrtf(__builtin_fmaf(ex, ex, ey * ey));   // 1 ulp: feeds the closeness value only
@@ -838,7 +840,7 @@ __device__ inline void lidar_point(float* lds, int lane, float rxf, float ryf, f
   const int bp = (bin + 1) & 15, bm = (bin + 15) & 15;
   // closeness values are >= +0, so their bit patterns order like the floats: LDS integer
   // atomic max (ds_max_i32, no return value) replaces read-max-write and its round trips
-  int* o = reinterpret_cast<int*>(&TILE(0));
+  int* o = reinterpret_cast<int*>(lds + tile_base + lane);
   atomicMax(o + bin * WAVE, __float_as_int(sensor));
   atomicMax(o + bp * WAVE, __float_as_int(alias * sensor));
   atomicMax(o + bm * WAVE, __float_as_int((1.0f - alias) * sensor));
@@ -935,6 +937,36 @@ __device__ __attribute__((noinline)) void dg_free_body_finish(float* B, bool is_
 // MODE_POST: Doggo only - the generic step after the wave-cooperative physics kernel (results in StepArgs::DR):
 // no physics code in the instance at all
 enum { MODE_ALL = 0, MODE_QUIET = 1, MODE_BUSY = 2, MODE_POST = 3 };
+
+// ---- LDS budget of the observation epilogue (step_body), shared by the kernels and the host launcher --------------------
+// Chunked form: the region from the yaw rows on is one staging tile per 16-column chunk ([bin][lane] for a lidar chunk,
+// [lane][STG_STRIDE] for the sensors), stored and reused chunk after chunk.
+// Whole-row form (obs_whole_rows): an instance without buttons and without a task object never puts a point into the
+// objects chunk, so its row has OBS_DIM - 16 staged columns; where those fit as [column][lane] rows into the LDS the kernel
+// owns anyway, the whole row is staged once and leaves in ONE store phase of OBS_DIM / 4 float4 per lane:
+//   rows 0 .. T0 - 1    goal tile (16), then the sensor columns: written after the obstacle lidar has read the x / y rows
+//                       of the free bodies for the last time (the yaw rows die at the first barrier of the epilogue)
+//   rows T0 .. T0 + 15  obstacle tile, T0 = staged columns - 16 >= 2 NBODY: it accumulates while x / y are still read
+constexpr int obs_dim(int robot) { return robot == SAG_ROBOT_DOGGO ? 104 : (robot == SAG_ROBOT_CAR ? 72 : 60); }
+constexpr int quiet_lds_rows_chunked(int robot) { return LS_YAW + (robot == SAG_ROBOT_CAR ? 25 : 17); }
+// Bytes of LDS a quiet workgroup holds, static + dynamic: its chunked array padded in 512-B steps up to a Point busy
+// workgroup's lds[] + rows[] (sag_step_device: why).  The co-scheduling of the two kernels has a sharp optimum at this
+// figure (13 568 B for both robots): it does not move when the quiet array grows, the dynamic part shrinks instead.
+constexpr int quiet_lds_total(int robot) {
+  const int own = quiet_lds_rows_chunked(robot) * WAVE * (int)sizeof(float), busy = (LDS_FLOATS + WAVE) * (int)sizeof(float);
+  return busy > own ? own + (busy - own + 511) / 512 * 512 : own;
+}
+constexpr bool obs_whole_rows(int robot, bool has_btn, bool has_tbox, int mode) {
+  const int cols = obs_dim(robot) - 16;
+  return robot != SAG_ROBOT_DOGGO && mode != MODE_POST && !has_btn && !has_tbox && cols - 16 >= 2 * NBODY &&
+         cols <= LDS_SLOTS &&                                                  // lds[] of k_step, k_step_busy, k_observe_rows
+         cols * WAVE * (int)sizeof(float) <= quiet_lds_total(robot);          // lds[] of k_step_quiet
+}
+// rows of k_step_quiet's lds[]
+constexpr int quiet_lds_rows(int robot, bool has_btn, bool has_tbox) {
+  const int chunked = quiet_lds_rows_chunked(robot), whole = obs_dim(robot) - 16;
+  return obs_whole_rows(robot, has_btn, has_tbox, MODE_QUIET) && whole > chunked ? whole : chunked;
+}
 // two copies of the busy bit, used alternately (StepArgs::phase): a launch reads bit 28 + phase and
 // writes bit 28 + (phase ^ 1), so the QUIET launch cannot re-flag an env for the BUSY launch of
 // the same step
@@ -2026,7 +2058,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
   if (!p.observe_only && live) I[iaddr(DI_TSTATE, (size_t)N, (size_t)i)] = (int32_t)tstate;
   if constexpr (MODE != MODE_ALL && !DOGGO) {
     // an env that will be busy next step leaves its hot record behind (positions still in LDS here:
-    // the observation staging below reuses the yaw rows)
+    // the observation staging below reuses the yaw rows, and in its whole-row form the x / y rows as well)
     if (p.hot && busy_next && live && !p.observe_only) {
       float4* __restrict__ Hw = reinterpret_cast<float4*>(p.hot) + (size_t)i * HOT_GROUPS;
       Hw[0] = make_float4(R.x, R.y, yaw, R.vx);
@@ -2111,103 +2143,185 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       }
     }
     __syncthreads();  // physics is done with the yaw / pool slots everywhere in the wavefront
-#pragma unroll 1
-    for (int chunk = 0; chunk < NCHUNK; chunk++) {
-      if (chunk < 3) {
+    if constexpr (obs_whole_rows(ROBOT, HAS_BTN, HAS_TBOX, MODE)) {
+      // ---- whole rows: every staged column of the row in LDS at once, one store phase (layout: obs_whole_rows) ----------
+      // From the barrier above to the one below every LDS access is to the lane's own column, so the tiles need no
+      // barrier between them; the empty objects chunk has no tile, its zeros come from registers.
+      constexpr int Q = OBS_DIM / 4, T0 = OBS_DIM - 32, R_GOAL = 0, R_SENS = 16;
+      static_assert(R_SENS + NSENS == T0 && T0 >= LS_YAW, "goal tile + sensors fill the rows below the obstacle tile");
+      static_assert(!CAR && !DOGGO && !HAS_BTN && !HAS_TBOX, "the Point's twelve sensor columns; no point ever falls into the objects chunk");
+      auto lid_at = [&](const int row, float px, float py) { lidar_point(lds, lane, R.x, R.y, yaw, cf, sf, px, py, row * WAVE); };
 #pragma unroll
-        for (int k = 0; k < 16; k++) TILE(k) = 0.0f;
-      }
-      if (chunk == 0) {
+      for (int k = 0; k < 16; k++) LP(T0, k) = 0.0f;
 #pragma unroll 1
-        for (int k = 0; k < SAG_MAX_HAZARDS; k++)
-          if (k < nH) lid(hzx[k], hzy[k]);
+      for (int k = 0; k < SAG_MAX_HAZARDS; k++)
+        if (k < nH) lid_at(T0, hzx[k], hzy[k]);
 #pragma unroll 1
-        for (int k = 0; k < nV; k++)
-          lid(LP(LS_X, k), LP(LS_Y, k));
+      for (int k = 0; k < nV; k++)
+        lid_at(T0, LP(LS_X, k), LP(LS_Y, k));
 #pragma unroll 1
-        for (int k = 0; k < SAG_MAX_PILLARS; k++)
-          if (k < nP) lid(pick(stx, k), pick(sty, k));
-      } else if (chunk == 1 || chunk == 2) {
-        const int want = chunk == 1 ? 3 : 2;  // GROUP_OBJECTS then GROUP_GOAL (consts.py:13-16)
-        if (chunk == 1 && has_box) lid(boxx, boxy);
-#pragma unroll 1
-        for (int b = 0; b < (HAS_BTN ? SAG_MAX_BUTTONS : 0); b++) {
-          if (b < nB) {
-            int g;
-            if (task == SAG_TASK_COLLECT) g = (act >> b & 1) ? 2 : 0;
-            else g = bstate == 0 ? 0 : (b == gb ? 2 : 3);
-            if (g == want) lid(pick(stx, (SAG_MAX_PILLARS + b) % NSTAT), pick(sty, (SAG_MAX_PILLARS + b) % NSTAT));
-          }
-        }
-        if (chunk == 2 && nB == 0) lid(goalx, goaly);
-      } else if (DOGGO) {
-        for (int k = 0; k < 28; k++) STG(k) = dsens[(DOGGO ? (chunk - 3) * 28 : 0) + k];
-      } else if (chunk == 3) {
+      for (int k = 0; k < SAG_MAX_PILLARS; k++)
+        if (k < nP) lid_at(T0, pick(stx, k), pick(sty, k));
+      // the x / y rows of the free bodies were read for the last time: the goal tile and the sensors take them over
+#pragma unroll
+      for (int k = 0; k < 16; k++) LP(R_GOAL, k) = 0.0f;
+      lid_at(R_GOAL, goalx, goaly);
+      {
         const float qax = bad ? 0.0f : R.ax, qay = bad ? 0.0f : R.ay;
-        STG(0) = cf * qax + sf * qay;
-        STG(1) = cf * qay - sf * qax;
-        STG(2) = GRAV;
-        STG(3) = cf * R.vx + sf * R.vy;
-        STG(4) = cf * R.vy - sf * R.vx;
-        STG(5) = 0; STG(6) = 0; STG(7) = 0; STG(8) = R.w;
-        STG(9) = -0.5f * sf; STG(10) = -0.5f * cf; STG(11) = 0;
-        if constexpr (CAR) {
-          // ballangvel_rear in the ball's own frame, then the 3x3 of ballquat_rear, row-major
-          const float qw = ext[5], qx = ext[6], qy = ext[7], qz = ext[8];
-          const float Rm[9] = {qw * qw + qx * qx - qy * qy - qz * qz, 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy),
-                               2 * (qx * qy + qw * qz), qw * qw - qx * qx + qy * qy - qz * qz, 2 * (qy * qz - qw * qx),
-                               2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), qw * qw - qx * qx - qy * qy + qz * qz};
-#pragma unroll
-          for (int k = 0; k < 3; k++) STG(12 + k) = Rm[k] * ext[2] + Rm[3 + k] * ext[3] + Rm[6 + k] * ext[4];
-#pragma unroll
-          for (int k = 0; k < 9; k++) STG(15 + k) = Rm[k];
-        }
+        LP(R_SENS, 0) = cf * qax + sf * qay;
+        LP(R_SENS, 1) = cf * qay - sf * qax;
+        LP(R_SENS, 2) = GRAV;
+        LP(R_SENS, 3) = cf * R.vx + sf * R.vy;
+        LP(R_SENS, 4) = cf * R.vy - sf * R.vx;
+        LP(R_SENS, 5) = 0; LP(R_SENS, 6) = 0; LP(R_SENS, 7) = 0; LP(R_SENS, 8) = R.w;
+        LP(R_SENS, 9) = -0.5f * sf; LP(R_SENS, 10) = -0.5f * cf; LP(R_SENS, 11) = 0;
       }
       __syncthreads();
       CYC(CY_LIDAR);
+      // envs of the wavefront whose row this launch writes (row_ok as a mask)
+      const uint64_t ok_mask = ~skip_mask & (nvalid >= WAVE ? ~0ull : (1ull << nvalid) - 1ull);
       if (obs_vec) {
-        // 16 B per lane per store: a quarter of the store instructions of the dword form (rows are 240 /
-        // 288 / 416 B and chunks 64 B or NSENS floats: every piece starts on a 16-B boundary)
-        constexpr int Q = OBS_DIM / 4;
-        const int nq = chunk < 3 ? 4 : NSENS / 4, q0 = chunk < 3 ? 4 * chunk : 12 + (chunk - 3) * (NSENS / 4);
-        float4* __restrict__ o4 = reinterpret_cast<float4*>(o);
-#pragma unroll 1
-        for (int j = 0; j < nq; j++) {
-          const int e = j * WAVE + lane;
-          const int env = nq == 4 ? e >> 2 : (nq == 3 ? (int)(((uint32_t)e * 21846u) >> 16) : (nq == 6 ? (int)(((uint32_t)e * 10923u) >> 16)
-                                                                                                    : (int)(((uint32_t)e * 9363u) >> 16)));
-          const int c4 = e - env * nq;   // e / nq exact for e < 64 nq (nq = 3, 4, 6, 7)
-          float4 v;
-          if (chunk < 3) {   // [bin][lane] tile: the env's four bins of this quarter are WAVE floats apart
-            const float* t = lds + STG_BASE + (4 * c4) * WAVE + env;
-            v = make_float4(t[0], t[WAVE], t[2 * WAVE], t[3 * WAVE]);
-          } else {
-            const float* t = lds + STG_BASE + env * STG_STRIDE + 4 * c4;
-            v = make_float4(t[0], t[1], t[2], t[3]);
-          }
-          if (row_ok(env)) o4[row_of(env) * Q + q0 + c4] = v;
+        // Four lanes write a 64-B run, and the lane group g = lane / 4 owns the rows of envs 4 g .. 4 g + 3: 4 Q float4
+        // that are contiguous in ALL / QUIET, so store j of a lane is float4 4 j + pos of that block - one address per
+        // lane and the immediate offsets 64 j.  With j a constant after unrolling, the env (el of the group's four) and
+        // the float4 of its row (c4) of each of the four lanes are constants too; a row boundary inside the run (wrap)
+        // costs a select.  The transposed read hits a bank (the env) with at most four addresses, as the chunked form did.
+        const int g = lane >> 2, pos = lane & 3;
+        const uint32_t nib = (uint32_t)(ok_mask >> (4 * g)) & 15u;
+        const bool ok[5] = {(nib & 1u) != 0, (nib & 2u) != 0, (nib & 4u) != 0, (nib & 8u) != 0, false};
+        int row_id[5] = {0, 0, 0, 0, 0};
+        if constexpr (MODE == MODE_BUSY) {
+#pragma unroll
+          for (int k = 0; k < 4; k++) row_id[k] = rows[4 * g + k];
         }
-      } else if (chunk < 3) {
-#pragma unroll 4
-        for (int j = 0; j < 16; j++) {
-          const int e = j * WAVE + lane, env = e >> 4, col = e & 15;
-          const float v = lds[STG_BASE + col * WAVE + env];
-          if (row_ok(env)) o[row_of(env) * OBS_DIM + chunk * 16 + col] = v;
+        float4* __restrict__ o4 = reinterpret_cast<float4*>(o);
+        float4* __restrict__ ob = o4 + ((size_t)base_env + 4 * g) * Q + pos;
+        const float* tb = lds + 4 * g;
+#pragma unroll
+        for (int j = 0; j < Q; j++) {
+          const int c0 = (4 * j) % Q, el0 = (4 * j) / Q;
+          const bool wrap = pos >= Q - c0;   // the next env's row has begun
+          const int c4 = c0 + pos - (wrap ? Q : 0), el = el0 + (wrap ? 1 : 0);
+          const bool zeros = c4 >= 4 && c4 < 8;   // the objects chunk
+          const int row = c4 < 4 ? T0 + 4 * c4 : (zeros ? 0 : 4 * (c4 - 8));
+          const float* t = tb + row * WAVE + el;
+          float4 v = make_float4(t[0], t[WAVE], t[2 * WAVE], t[3 * WAVE]);
+          if (zeros) v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (wrap ? ok[el0 + 1] : ok[el0]) {
+            if constexpr (MODE == MODE_BUSY) o4[(size_t)(wrap ? row_id[el0 + 1] : row_id[el0]) * Q + c4] = v;
+            else ob[4 * j] = v;
+          }
         }
       } else {
-#pragma unroll 4
-        for (int j = 0; j < NSENS; j++) {
-          const int e = j * WAVE + lane;
-          // e / 12 (e < 768), e / 24 (e < 1536) or e / 28 (e < 1792), exact
-          const int env = NSENS == 28 ? (int)(((uint32_t)e * 2341u) >> 16)
-                                      : (int)(((uint32_t)e * 43691u) >> (NSENS == 12 ? 19 : 20));
-          const int col = e - env * NSENS;
-          const float v = lds[STG_BASE + env * STG_STRIDE + col];
-          if (row_ok(env)) o[row_of(env) * OBS_DIM + 48 + (chunk - 3) * NSENS + col] = v;
+        // the caller's buffer is not 16-B aligned: the same tiles, dword by dword
+#pragma unroll 1
+        for (int e = lane; e < WAVE * OBS_DIM; e += WAVE) {
+          const int env = e / OBS_DIM, col = e - env * OBS_DIM;
+          const bool zeros = col >= 16 && col < 32;
+          const float v = lds[(col < 16 ? T0 + col : (zeros ? 0 : col - 32)) * WAVE + env];
+          if (ok_mask >> env & 1ull) o[row_of(env) * OBS_DIM + col] = zeros ? 0.0f : v;
         }
       }
-      __syncthreads();
       CYC(CY_OBS_STORE);
+    } else {
+#pragma unroll 1
+      for (int chunk = 0; chunk < NCHUNK; chunk++) {
+        if (chunk < 3) {
+#pragma unroll
+          for (int k = 0; k < 16; k++) TILE(k) = 0.0f;
+        }
+        if (chunk == 0) {
+#pragma unroll 1
+          for (int k = 0; k < SAG_MAX_HAZARDS; k++)
+            if (k < nH) lid(hzx[k], hzy[k]);
+#pragma unroll 1
+          for (int k = 0; k < nV; k++)
+            lid(LP(LS_X, k), LP(LS_Y, k));
+#pragma unroll 1
+          for (int k = 0; k < SAG_MAX_PILLARS; k++)
+            if (k < nP) lid(pick(stx, k), pick(sty, k));
+        } else if (chunk == 1 || chunk == 2) {
+          const int want = chunk == 1 ? 3 : 2;  // GROUP_OBJECTS then GROUP_GOAL (consts.py:13-16)
+          if (chunk == 1 && has_box) lid(boxx, boxy);
+#pragma unroll 1
+          for (int b = 0; b < (HAS_BTN ? SAG_MAX_BUTTONS : 0); b++) {
+            if (b < nB) {
+              int g;
+              if (task == SAG_TASK_COLLECT) g = (act >> b & 1) ? 2 : 0;
+              else g = bstate == 0 ? 0 : (b == gb ? 2 : 3);
+              if (g == want) lid(pick(stx, (SAG_MAX_PILLARS + b) % NSTAT), pick(sty, (SAG_MAX_PILLARS + b) % NSTAT));
+            }
+          }
+          if (chunk == 2 && nB == 0) lid(goalx, goaly);
+        } else if (DOGGO) {
+          for (int k = 0; k < 28; k++) STG(k) = dsens[(DOGGO ? (chunk - 3) * 28 : 0) + k];
+        } else if (chunk == 3) {
+          const float qax = bad ? 0.0f : R.ax, qay = bad ? 0.0f : R.ay;
+          STG(0) = cf * qax + sf * qay;
+          STG(1) = cf * qay - sf * qax;
+          STG(2) = GRAV;
+          STG(3) = cf * R.vx + sf * R.vy;
+          STG(4) = cf * R.vy - sf * R.vx;
+          STG(5) = 0; STG(6) = 0; STG(7) = 0; STG(8) = R.w;
+          STG(9) = -0.5f * sf; STG(10) = -0.5f * cf; STG(11) = 0;
+          if constexpr (CAR) {
+            // ballangvel_rear in the ball's own frame, then the 3x3 of ballquat_rear, row-major
+            const float qw = ext[5], qx = ext[6], qy = ext[7], qz = ext[8];
+            const float Rm[9] = {qw * qw + qx * qx - qy * qy - qz * qz, 2 * (qx * qy - qw * qz), 2 * (qx * qz + qw * qy),
+                                 2 * (qx * qy + qw * qz), qw * qw - qx * qx + qy * qy - qz * qz, 2 * (qy * qz - qw * qx),
+                                 2 * (qx * qz - qw * qy), 2 * (qy * qz + qw * qx), qw * qw - qx * qx - qy * qy + qz * qz};
+#pragma unroll
+            for (int k = 0; k < 3; k++) STG(12 + k) = Rm[k] * ext[2] + Rm[3 + k] * ext[3] + Rm[6 + k] * ext[4];
+#pragma unroll
+            for (int k = 0; k < 9; k++) STG(15 + k) = Rm[k];
+          }
+        }
+        __syncthreads();
+        CYC(CY_LIDAR);
+        if (obs_vec) {
+          // 16 B per lane per store: a quarter of the store instructions of the dword form (rows are 240 /
+          // 288 / 416 B and chunks 64 B or NSENS floats: every piece starts on a 16-B boundary)
+          constexpr int Q = OBS_DIM / 4;
+          const int nq = chunk < 3 ? 4 : NSENS / 4, q0 = chunk < 3 ? 4 * chunk : 12 + (chunk - 3) * (NSENS / 4);
+          float4* __restrict__ o4 = reinterpret_cast<float4*>(o);
+#pragma unroll 1
+          for (int j = 0; j < nq; j++) {
+            const int e = j * WAVE + lane;
+            const int env = nq == 4 ? e >> 2 : (nq == 3 ? (int)(((uint32_t)e * 21846u) >> 16) : (nq == 6 ? (int)(((uint32_t)e * 10923u) >> 16)
+                                                                                                      : (int)(((uint32_t)e * 9363u) >> 16)));
+            const int c4 = e - env * nq;   // e / nq exact for e < 64 nq (nq = 3, 4, 6, 7)
+            float4 v;
+            if (chunk < 3) {   // [bin][lane] tile: the env's four bins of this quarter are WAVE floats apart
+              const float* t = lds + STG_BASE + (4 * c4) * WAVE + env;
+              v = make_float4(t[0], t[WAVE], t[2 * WAVE], t[3 * WAVE]);
+            } else {
+              const float* t = lds + STG_BASE + env * STG_STRIDE + 4 * c4;
+              v = make_float4(t[0], t[1], t[2], t[3]);
+            }
+            if (row_ok(env)) o4[row_of(env) * Q + q0 + c4] = v;
+          }
+        } else if (chunk < 3) {
+#pragma unroll 4
+          for (int j = 0; j < 16; j++) {
+            const int e = j * WAVE + lane, env = e >> 4, col = e & 15;
+            const float v = lds[STG_BASE + col * WAVE + env];
+            if (row_ok(env)) o[row_of(env) * OBS_DIM + chunk * 16 + col] = v;
+          }
+        } else {
+#pragma unroll 4
+          for (int j = 0; j < NSENS; j++) {
+            const int e = j * WAVE + lane;
+            // e / 12 (e < 768), e / 24 (e < 1536) or e / 28 (e < 1792), exact
+            const int env = NSENS == 28 ? (int)(((uint32_t)e * 2341u) >> 16)
+                                        : (int)(((uint32_t)e * 43691u) >> (NSENS == 12 ? 19 : 20));
+            const int col = e - env * NSENS;
+            const float v = lds[STG_BASE + env * STG_STRIDE + col];
+            if (row_ok(env)) o[row_of(env) * OBS_DIM + 48 + (chunk - 3) * NSENS + col] = v;
+          }
+        }
+        __syncthreads();
+        CYC(CY_OBS_STORE);
+      }
     }
   }
   if (live) {
@@ -2265,10 +2379,11 @@ __global__ __launch_bounds__(WAVE, 1) void k_step_doggo_post(StepArgs p) {
 #endif
 template <int ROBOT, bool HAS_BTN, bool HAS_TBOX>
 __global__ __launch_bounds__(WAVE, ROBOT == SAG_ROBOT_CAR ? SAG_CAR_QUIET_MIN_WAVES : SAG_QUIET_MIN_WAVES) void k_step_quiet(StepArgs p) {
-  // positions (x, y) of the free bodies + the observation staging tile; no dynamic pool:
-  // 10 KB (Point) -> 16 wavefronts per CU
-  constexpr int QSLOTS = LS_YAW + (ROBOT == SAG_ROBOT_CAR ? 25 : 17);
+  // positions (x, y) of the free bodies + the observation staging (one chunk's tile, or the whole row where it fits:
+  // obs_whole_rows); no dynamic pool.  The launch pads it to quiet_lds_total with dynamic LDS that nobody touches.
+  constexpr int QSLOTS = quiet_lds_rows(ROBOT, HAS_BTN, HAS_TBOX);
   static_assert(QSLOTS >= LS_YAW + NBODY, "the yaw rows written at load time must stay in bounds");
+  static_assert(QSLOTS * WAVE * (int)sizeof(float) <= quiet_lds_total(ROBOT), "the quiet array stays inside the footprint of its launch");
   __shared__ float lds[QSLOTS * WAVE];
   const int lane = threadIdx.x, base = blockIdx.x * WAVE, gi = base + lane;
   const bool in = gi < p.N;
