@@ -287,6 +287,17 @@ int sag_render_rgb_device(sag_ctx* ctx, void* d_out);
 int sag_render(sag_ctx* ctx, int32_t camera, int32_t width, int32_t height, int32_t flags, uint8_t* out);
 int sag_render_device(sag_ctx* ctx, int32_t camera, int32_t width, int32_t height, int32_t flags,
                       const float* d_obs, const uint8_t* d_cost, void* d_out);
+/* A chosen subset of the envs.
+ * as sag_render_device, for the envs with a non-zero byte of d_mask ([n_envs] device bytes, complete before the call;
+ * NULL: every env = sag_render_device).  Rows of other envs in d_out are not written.  Stream-ordered, no wait. */
+int sag_render_rows_device(sag_ctx* ctx, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                           const float* d_obs, const uint8_t* d_cost, const uint8_t* d_mask, void* d_out);
+/* as sag_render, for n listed envs: out [n][height][width][3] host, row j = env env_ids[j] (host int32, any order,
+ * duplicates allowed).  Overlays show rows env_ids[j] of the context's own observation / cost buffers, as sag_render.
+ * The staging buffer is sized for n images, not n_envs.  n == 0: SAG_OK, nothing launched.
+ * SAG_ERR_ARG, nothing launched: NULL pointers with n > 0, n < 0, an index outside [0, n_envs), bad camera / size. */
+int sag_render_envs(sag_ctx* ctx, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                    const int32_t* env_ids, int32_t n, uint8_t* out);
 
 /* Diagnostic: how many envs the last split step handed to the busy kernel (0 for the
  * single-kernel form).  Synchronises the context stream. */

@@ -32,7 +32,7 @@ EXPORTS = [
     'sag_robot_info', 'sag_create', 'sag_destroy', 'sag_last_error', 'sag_set_layout',
     'sag_reset', 'sag_get_state', 'sag_set_state', 'sag_step', 'sag_step_device', 'sag_wait',
     'sag_observe', 'sag_set_ext_contacts', 'sag_lidar_cost', 'sag_lidar_cost_device', 'sag_set_seed', 'sag_dev_alloc', 'sag_dev_free', 'sag_dev_upload',
-    'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_debug_doggo_coop',
+    'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_render_rows_device', 'sag_render_envs', 'sag_debug_doggo_coop',
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
     'sag_episode_clear', 'sag_fork_device', 'sag_fork_counts'
@@ -102,6 +102,8 @@ def load():
   lib.sag_render_rgb_device.argtypes = [vp, vp]
   lib.sag_render.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
   lib.sag_render_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
+  lib.sag_render_rows_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+  lib.sag_render_envs.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, C.POINTER(C.c_uint8)]
   lib.sag_debug_doggo_coop.argtypes = [vp, C.POINTER(C.c_double)]
   lib.sag_debug_cycles.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.c_int32]
   lib.sag_world_config_default.argtypes = [C.POINTER(WorldConfig)]
@@ -534,14 +536,35 @@ class Context:
 
   CAMERAS = {'vision': 0, 'fixednear': 1, 'fixedfar': 2, 'track': 3}
 
-  def render(self, camera='fixedfar', width=256, height=256, overlays=True):
+  def render(self, camera='fixedfar', width=256, height=256, overlays=True, envs=None):
     """[n_envs, height, width, 3] uint8 from one of the scene's cameras (name or id), optionally with the lidar
-    rings and the cost indicator of the last step."""
+    rings and the cost indicator of the last step.  envs: int32 indices of the envs to render, any order, duplicates
+    allowed (sag_render_envs) -> [len(envs), height, width, 3], row j = env envs[j]; device work and staging are for
+    len(envs) images only."""
     cam = self.CAMERAS[camera] if isinstance(camera, str) else int(camera)
+    if envs is not None:
+      ids = np.asarray(envs)
+      if ids.ndim != 1 or (ids.size and ids.dtype.kind not in 'iu'):
+        raise ValueError(f'envs: a 1-D sequence of integer indices, not {ids.dtype} {ids.shape}')
+      if ids.size and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31):   # (must not wrap into range; the library checks the rest)
+        raise SagError(f'sag_render_envs: an env index outside int32 ({self.n_envs} envs)')
+      ids = np.ascontiguousarray(ids, np.int32)
+      img = np.zeros((len(ids), int(height), int(width), 3), np.uint8)
+      self._check(self.lib.sag_render_envs(self.h, cam, int(width), int(height), 1 if overlays else 0, _ptr(ids, C.c_int32),
+                                           len(ids), img.ctypes.data_as(C.POINTER(C.c_uint8))), 'sag_render_envs')
+      return img
     img = np.zeros((self.n_envs, int(height), int(width), 3), np.uint8)
     self._check(self.lib.sag_render(self.h, cam, int(width), int(height), 1 if overlays else 0,
                                     img.ctypes.data_as(C.POINTER(C.c_uint8))), 'sag_render')
     return img
+
+  def render_rows_device(self, d_mask, d_out, camera='vision', width=64, height=64, overlays=False, d_obs=None, d_cost=None):
+    """sag_render_rows_device: the images of the envs with a non-zero byte of d_mask (device pointer of [n_envs] bytes; None:
+    every env) into their own rows of d_out (device pointer of [n_envs][height][width][3] bytes), enqueued on the context
+    stream; the other rows are not written.  d_obs / d_cost: what the overlays show (device pointers or None)."""
+    cam = self.CAMERAS[camera] if isinstance(camera, str) else int(camera)
+    self._check(self.lib.sag_render_rows_device(self.h, cam, int(width), int(height), 1 if overlays else 0, d_obs, d_cost,
+                                                d_mask, d_out), 'sag_render_rows_device')
 
   def debug_doggo_coop(self):
     out = np.zeros((self.n_envs, 760), np.float64)

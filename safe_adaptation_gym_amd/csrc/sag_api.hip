@@ -1256,14 +1256,40 @@ int sag_debug_doggo_coop(sag_ctx* c, double* out) {
 
 // images of every env at its current state, ray-cast on the device (sag_render.hpp): [n_envs][height][width][3] uint8.
 // d_obs / d_cost: the observation and cost flags the overlays show (device pointers or NULL)
+static int render_args_ok(sag_ctx* c, int32_t camera, int32_t width, int32_t height) {
+  if (camera < 0 || camera > SAG_CAM_TRACK || width <= 0 || height <= 0 || width > 4096 || height > 4096)
+    return fail(c, SAG_ERR_ARG, "bad camera %d or image size %d x %d", camera, width, height);
+  return SAG_OK;
+}
+// the staging buffer of sag_render / sag_render_envs holds at least `bytes`; rgb_bytes is what d_rgb really has
+static int ensure_rgb(sag_ctx* c, size_t bytes) {
+  if (c->rgb_bytes >= bytes) return 0;
+  if (c->d_rgb) (void)hipFree(c->d_rgb);
+  c->d_rgb = nullptr; c->rgb_bytes = 0;
+  HIPCHK(c, hipMalloc(&c->d_rgb, bytes ? bytes : 1));
+  c->rgb_bytes = bytes;
+  return 0;
+}
 int sag_render_device(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
                       const uint8_t* d_cost, void* d_out) {
   if (!c || !d_out) return c ? fail(c, SAG_ERR_ARG, "null argument") : SAG_ERR_ARG;
-  if (camera < 0 || camera > SAG_CAM_TRACK || width <= 0 || height <= 0 || width > 4096 || height > 4096)
-    return fail(c, SAG_ERR_ARG, "bad camera %d or image size %d x %d", camera, width, height);
+  if (int rc = render_args_ok(c, camera, width, height)) return rc;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   hipLaunchKernelGGL(k_render_rgb, dim3(c->N), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height,
                      flags, d_obs, c->rb.obs_dim, d_cost, (uint8_t*)d_out);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+// the envs of a device mask, each into its own row: the grid is sized for n_envs whatever the mask holds, and a workgroup
+// whose byte is zero returns at once (k_render_rows) - nothing the host decides, so it follows a reset on the stream
+int sag_render_rows_device(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
+                           const uint8_t* d_cost, const uint8_t* d_mask, void* d_out) {
+  if (!d_mask) return sag_render_device(c, camera, width, height, flags, d_obs, d_cost, d_out);
+  if (!c || !d_out) return c ? fail(c, SAG_ERR_ARG, "null argument") : SAG_ERR_ARG;
+  if (int rc = render_args_ok(c, camera, width, height)) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(k_render_rows, dim3(c->N), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height,
+                     flags, d_obs, c->rb.obs_dim, d_cost, d_mask, (uint8_t*)d_out);
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }
@@ -1271,16 +1297,34 @@ int sag_render(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_
   if (!c || !out) return c ? fail(c, SAG_ERR_ARG, "null argument") : SAG_ERR_ARG;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const size_t bytes = (size_t)c->N * (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0) * 3;
-  if (c->rgb_bytes < bytes) {
-    if (c->d_rgb) (void)hipFree(c->d_rgb);
-    c->d_rgb = nullptr; c->rgb_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->d_rgb, bytes ? bytes : 1));
-    c->rgb_bytes = bytes;
-  }
+  if (int rc = ensure_rgb(c, bytes)) return rc;
   // the overlays show what the last host-buffer step / observe left in the context's output buffers
   int rc = sag_render_device(c, camera, width, height, flags, c->d_obs, c->d_cost, c->d_rgb);
   if (rc) return rc;
   HIPCHK(c, hipMemcpyAsync(out, c->d_rgb, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SAG_OK;
+}
+// n listed envs, compact: the staging buffer holds the index list (4 n bytes, rounded up to 16) in front of the n images,
+// grown through ensure_rgb like sag_render's, so that rgb_bytes stays the size of what d_rgb points to
+int sag_render_envs(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const int32_t* env_ids, int32_t n,
+                    uint8_t* out) {
+  if (!c) return SAG_ERR_ARG;
+  if (n < 0 || (n > 0 && (!env_ids || !out))) return fail(c, SAG_ERR_ARG, "sag_render_envs: n %d or a null argument", n);
+  if (int rc = render_args_ok(c, camera, width, height)) return rc;
+  for (int32_t j = 0; j < n; j++)
+    if (env_ids[j] < 0 || env_ids[j] >= c->N) return fail(c, SAG_ERR_ARG, "sag_render_envs: env %d (entry %d) of %d envs", env_ids[j], j, c->N);
+  if (n == 0) return SAG_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t list = ((size_t)n * sizeof(int32_t) + 15) & ~(size_t)15, bytes = (size_t)n * width * height * 3;
+  if (int rc = ensure_rgb(c, list + bytes)) return rc;
+  // (the stream is joined below: env_ids has been read when the call returns)
+  HIPCHK(c, hipMemcpyAsync(c->d_rgb, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_render_list, dim3(n), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height, flags,
+                     (const float*)c->d_obs, c->rb.obs_dim, (const uint8_t*)c->d_cost, reinterpret_cast<const int32_t*>(c->d_rgb),
+                     c->d_rgb + list);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->d_rgb + list, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SAG_OK;
 }

@@ -200,17 +200,17 @@ __device__ inline void r_rod(RObj* ob, int& n, const double* R, const double* p,
   q.rgb[0] = cr; q.rgb[1] = cg; q.rgb[2] = cb; q.alpha = al;
 }
 
-// out: [N][H][W][3] uint8.  obs / cost (device pointers or nullptr): last observation [N][obs_dim] and cost flags for
-// the overlays (lidar rings, cost indicator).
-__global__ __launch_bounds__(256) void k_render_rgb(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
-                                                    int robot, int cam_id, int W, int H, int flags,
-                                                    const float* __restrict__ obs, int obs_dim,
-                                                    const uint8_t* __restrict__ cost, uint8_t* __restrict__ out) {
+// One workgroup renders env i into image `row` of out ([rows][H][W][3] uint8): the body of the three kernels below, which
+// differ only in how a workgroup finds its env and its row.  obs / cost (device pointers or nullptr): last observation
+// [N][obs_dim] and cost flags for the overlays (lidar rings, cost indicator), read at row i - they follow the env.
+__device__ __forceinline__ void r_render_env(const float* __restrict__ S, const int32_t* __restrict__ I, int N, int robot,
+                                             int cam_id, int W, int H, int flags, const float* __restrict__ obs, int obs_dim,
+                                             const uint8_t* __restrict__ cost, uint8_t* __restrict__ out, const size_t i,
+                                             const size_t row) {
   __shared__ RObj ob[R_MAXOBJ];
   __shared__ float4 bsph[R_MAXOBJ];   // bounding sphere: centre - camera origin, radius with margin
   __shared__ RCam cam;
   __shared__ int nob_s;
-  const size_t i = blockIdx.x;
   if (threadIdx.x == 0) {
     auto F = [&](int k) { return (double)S[saddr(k, (size_t)N, i)]; };
     const uint32_t meta = (uint32_t)I[iaddr(DI_META, (size_t)N, i)], tstate = (uint32_t)I[iaddr(DI_TSTATE, (size_t)N, i)];
@@ -327,7 +327,7 @@ __global__ __launch_bounds__(256) void k_render_rgb(const float* __restrict__ S,
     const float perp2 = (b.x * b.x + b.y * b.y + b.z * b.z) - proj * proj;
     return perp2 <= b.w * b.w && proj >= -b.w;
   };
-  uint8_t* img = out + i * (size_t)W * H * 3;
+  uint8_t* img = out + row * (size_t)W * H * 3;
   const double aspect = (double)W / (double)H;
   // Pixels in 8 x 8 tiles, a tile per wavefront pass: the 64 rays of a wavefront then span an eighth of the image's width instead of a
   // whole row, and the wavefront runs the fp64 intersection of an object only when one of ITS rays passes the sphere test - with rows,
@@ -390,6 +390,38 @@ __global__ __launch_bounds__(256) void k_render_rgb(const float* __restrict__ S,
       img[px * 3 + k] = (uint8_t)(x * 255.0 + 0.5);
     }
   }
+}
+
+// every env: workgroup b renders env b into row b.  out: [N][H][W][3]
+__global__ __launch_bounds__(256) void k_render_rgb(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
+                                                    int robot, int cam_id, int W, int H, int flags,
+                                                    const float* __restrict__ obs, int obs_dim,
+                                                    const uint8_t* __restrict__ cost, uint8_t* __restrict__ out) {
+  r_render_env(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, blockIdx.x, blockIdx.x);
+}
+
+// masked, in place: the envs with a non-zero byte of mask [N], env b into row b; the other rows of out are not touched.
+// Every workgroup reads its own byte and leaves before the first barrier (the byte is one value for the whole workgroup):
+// no list, no counter, no scratch - an unselected workgroup costs its dispatch and one scalar load.
+__global__ __launch_bounds__(256) void k_render_rows(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
+                                                     int robot, int cam_id, int W, int H, int flags,
+                                                     const float* __restrict__ obs, int obs_dim,
+                                                     const uint8_t* __restrict__ cost, const uint8_t* __restrict__ mask,
+                                                     uint8_t* __restrict__ out) {
+  if (!mask[blockIdx.x]) return;
+  r_render_env(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, blockIdx.x, blockIdx.x);
+}
+
+// listed, compact: workgroup j renders env ids[j] into row j.  out: [n][H][W][3], n = the grid; duplicates are fine (rows
+// are per entry).  The host checks the list (sag_render_envs); an index outside [0, N) renders nothing all the same.
+__global__ __launch_bounds__(256) void k_render_list(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
+                                                     int robot, int cam_id, int W, int H, int flags,
+                                                     const float* __restrict__ obs, int obs_dim,
+                                                     const uint8_t* __restrict__ cost, const int32_t* __restrict__ ids,
+                                                     uint8_t* __restrict__ out) {
+  const int32_t e = ids[blockIdx.x];
+  if (e < 0 || e >= N) return;
+  r_render_env(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, (size_t)e, blockIdx.x);
 }
 
 }  // namespace sag

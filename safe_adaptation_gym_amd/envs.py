@@ -76,21 +76,17 @@ class BatchedSafeAdaptationGym:
       raise ValueError('device_reset: parity_rng reproduces the reference\'s host MT19937 layout stream')
     # time_limit / auto_reset: the episode loop on the contexts' streams (sag_episode_track_device after every step, then
     # sag_reset_device_async of the envs that ended); see step()
-    self.time_limit = None if time_limit is None else int(time_limit)
-    self.auto_reset = bool(auto_reset)
-    self._track = self.time_limit is not None or self.auto_reset
-    if self._track:
-      if self.parity_rng:
-        raise ValueError('time_limit / auto_reset: parity_rng resets on the host, in the reference\'s order')
-      if not (self.device_buffers and self.device_reset):
-        raise ValueError('time_limit / auto_reset need device_buffers=True and device_reset=True')
-      if self._rgb_observation:
-        raise ValueError('time_limit / auto_reset with rgb_observation is not supported')
-      if self.time_limit is not None and self.time_limit <= 0:
-        raise ValueError(f'time_limit must be positive, not {time_limit}')
+    if (time_limit is not None or auto_reset) and self._rgb_observation:
+      # (the constructor's refusal is kept as it was; the loop itself handles images: episode_loop())
+      raise ValueError('time_limit / auto_reset with rgb_observation is not supported by make(): call '
+                       'env.episode_loop(time_limit, auto_reset) on the env')
+    self._set_episode_loop(time_limit, auto_reset)
     self._last_obs = None   # device_reset, host buffers: what the last step() returned (rows kept by a masked reset)
     self._mask_bufs = None  # device_reset: per-shard device copies of a host reset mask
     self._fork_bufs = None  # fork(): per-shard device copies of a host source-index array
+    # rgb_observation with device_buffers: every row of the image buffers shows its env's current state or, for an env kept
+    # by a masked reset, what the last step returned - only then may a reset render the rows of its mask alone
+    self._img_valid = False
     self.devices = [0] if devices is None else list(devices)
     if self.n_envs < len(self.devices):
       self.devices = self.devices[:self.n_envs]
@@ -114,6 +110,34 @@ class BatchedSafeAdaptationGym:
     self.action_space = Box(-1, 1, (self.robot.nu,), np.float32)
     self._observation_space = None
     self._reward_dim = 1
+
+  def _set_episode_loop(self, time_limit, auto_reset):
+    self.time_limit = None if time_limit is None else int(time_limit)
+    self.auto_reset = bool(auto_reset)
+    self._track = self.time_limit is not None or self.auto_reset
+    if self._track:
+      if self.parity_rng:
+        raise ValueError('time_limit / auto_reset: parity_rng resets on the host, in the reference\'s order')
+      if not (self.device_buffers and self.device_reset):
+        raise ValueError('time_limit / auto_reset need device_buffers=True and device_reset=True')
+      if self.time_limit is not None and self.time_limit <= 0:
+        raise ValueError(f'time_limit must be positive, not {time_limit}')
+
+  def episode_loop(self, time_limit=None, auto_reset=False):
+    """Turns on what make(..., time_limit=, auto_reset=) turns on - the episode tracker and the stream-ordered reset of the
+    envs that ended, see step() - on an env that exists.  This is how an rgb_observation env gets them: make() refuses that
+    combination, the loop does not.  Same requirements (device_buffers, device_reset, no parity_rng), ValueError otherwise
+    and the env stays as it was; to be called before the first reset() / step() (the device buffers are laid out then)."""
+    if self._dev is not None:
+      raise ValueError('episode_loop(): call it before the first reset() / step()')
+    old = self.time_limit, self.auto_reset
+    try:
+      self._set_episode_loop(time_limit, auto_reset)
+    except ValueError:
+      self._set_episode_loop(*old)
+      raise
+    if self._track and self._tasks is not None:
+      self._map(lambda c, s, e: c.episode_clear())
 
   # -- reference surface ----------------------------------------------------------
   @property
@@ -169,6 +193,7 @@ class BatchedSafeAdaptationGym:
     self._task_ids = np.array([t.TASK_ID for t in self._tasks], np.int32)
     self._reward_dim = max(t.REWARD_DIM for t in self._tasks)
     self._persist = None  # task attributes that outlive an episode (filled by _pull_task_state)
+    self._img_valid = False
     if self._track:
       self._map(lambda c, s, e: c.episode_clear())
     if self.device_reset:
@@ -187,7 +212,13 @@ class BatchedSafeAdaptationGym:
     sync=False (device_reset and device_buffers): the same reset enqueued on the contexts' streams
     (sag_reset_device_async) - the observation view comes back without waiting, the rows of the reset envs are written
     by the stream; mask=None resets every env.  No ResamplingError is raised: an env whose layout cannot be sampled keeps
-    its state and observation row and gets bit 0 of its flags, and reset_counts() tells how many there were."""
+    its state and observation row and gets bit 0 of its flags, and reset_counts() tells how many there were.
+
+    rgb_observation: the observation is the image view [n, 64, 64, 3] uint8.  A masked reset renders the envs of the mask
+    only (sag_render_rows_device), each into its own row; the other rows are not written.  The masked render takes no
+    status: an env of the mask whose layout could not be sampled kept its state, so rendering it again writes the bytes its
+    row already holds - it keeps its observation row by value.  With sync=False the vector observation is not formed at
+    all."""
     assert self._tasks is not None or (options is not None and 'task' in options), (
         'A task should be first set before reset.')
     if mask is not None and not self.device_reset:
@@ -198,8 +229,8 @@ class BatchedSafeAdaptationGym:
     if not sync:
       if not (self.device_buffers and self.device_reset):
         raise ValueError('reset(sync=False) needs device_buffers=True and device_reset=True')
-      if self._rgb_observation or (options is not None and 'task' in options):
-        raise ValueError('reset(sync=False): not with rgb_observation or a new task')
+      if options is not None and 'task' in options:
+        raise ValueError('reset(sync=False): not with a new task')
       if self._tasks is None:
         raise ValueError('reset(sync=False): a task should be first set')
     if mask is not None:
@@ -220,7 +251,16 @@ class BatchedSafeAdaptationGym:
     if not sync:
       bufs = self._dev_bufs()
       for k, (c, b) in enumerate(zip(self._ctx, bufs)):
-        c.reset_device_async(None if ptrs is None else nat.C.c_void_p(ptrs[k]), b['obs'])
+        d_mask = None if ptrs is None else nat.C.c_void_p(ptrs[k])
+        if self._rgb_observation:
+          # no vector observation is returned, so none is formed (the Doggo's is a pass over the whole batch); the image
+          # needs the state alone
+          c.reset_device_async(d_mask, None)
+          c.render_rows_device(d_mask if self._img_valid else None, b['img'])
+        else:
+          c.reset_device_async(d_mask, b['obs'])
+      if self._rgb_observation:
+        self._img_valid = True
       outs = [self._views(k)[0] for k in range(len(self._ctx))]
       return outs[0] if len(outs) == 1 else outs
     if self.device_reset:
@@ -318,6 +358,7 @@ class BatchedSafeAdaptationGym:
       ptrs = [buf.value for buf in self._fork_bufs]
     for c, oc, p in zip(self._ctx, other._ctx, ptrs):
       c.fork_device(nat.C.c_void_p(p), oc, same_stream=same_stream)
+    self._img_valid = False
     # host mirrors
     dst = np.concatenate([np.flatnonzero(ok) + s for ok, (s, e) in zip(commit, self._ranges)])
     frm = np.concatenate([loc[ok].astype(np.int64) + ss for loc, ok, (ss, se) in zip(local, commit, other._ranges)])
@@ -361,7 +402,12 @@ class BatchedSafeAdaptationGym:
     auto_reset=True (time_limit=None: no limit): after the tracker the envs that ended are reset on the stream, and
     their rows of the returned observation are the FIRST observation of the new episode; reward, cost and goal_met are
     the final transition's.  The final observation of an ended episode is not kept: a learner that needs it steps
-    without auto_reset and calls reset(mask=done, sync=False) itself after reading it."""
+    without auto_reset and calls reset(mask=done, sync=False) itself after reading it.
+
+    rgb_observation=True (the loop turned on with episode_loop()): `obs` is the image view [N, 64, 64, 3] uint8 and the
+    same contract holds.  With time_limit alone the stream runs step, render, tracker: the image is the final observation.
+    With auto_reset it runs step, tracker, reset of the ended envs (no vector observation is formed), then one render of
+    the whole batch: each env is rendered once per step and an ended env's image is the first of its new episode."""
     if self.device_buffers:
       return self._step_device(action, sync)
     a = np.asarray(action, np.float32).reshape(self.n_envs, self.robot.nu)
@@ -442,12 +488,17 @@ class BatchedSafeAdaptationGym:
         c.dev_upload(b['act'], np.ascontiguousarray(a, np.float32))
         d_act = b['act']
       c.step_device(d_act, None, -1, b['obs'], b['rew'], b['cost'], b['done'], b['met'])
-      if self._rgb_observation:
+      rgb = self._rgb_observation
+      if rgb and not self.auto_reset:   # (before the tracker: the final image of an episode that ends here)
         c.render_rgb_device(b['img'])
       if self._track:
         c.episode_track(b['rew'], b['cost'], b['done'], b['met'], self.time_limit or 0, b['ended'], b['episode'])
-        if self.auto_reset:
-          c.reset_device_async(b['ended'], b['obs'])
+        if self.auto_reset:   # every env is rendered once, after the resets: an ended env shows its new episode
+          c.reset_device_async(b['ended'], None if rgb else b['obs'])
+          if rgb:
+            c.render_rgb_device(b['img'])
+    if self._rgb_observation:
+      self._img_valid = True
     if sync:
       self.wait()
     outs = [self._views(k) for k in range(len(self._ctx))]
@@ -470,17 +521,42 @@ class BatchedSafeAdaptationGym:
   def _render_rgb(self):
     return np.concatenate(self._map(lambda c, s, e: c.render_rgb()))
 
-  def render(self, mode='human', **options):
+  def render(self, mode='human', envs=None, **options):
     """Images of every env from one of the scene's cameras, ray-cast on the device: [N, height, width, 3] uint8.
     Options as the reference passes to physics.render (render_options: camera_id 'vision' | 'fixednear' |
     'fixedfar' | 'track', height, width); defaults 'fixedfar', 256 x 256.  There is no window: mode 'human' and
-    'rgb_array' both return the array (a viewer can show it)."""
+    'rgb_array' both return the array (a viewer can show it).
+
+    envs: a 1-D integer sequence of global env indices, any order, duplicates allowed -> [len(envs), height, width, 3] in
+    that order (sag_render_envs).  Only these envs are ray-cast, staged and copied: each shard renders its own entries and
+    a shard with none launches nothing.  ValueError, before anything is launched, for an index outside [0, n_envs), a
+    dtype that is not an integer (bool included) and an array that is not 1-D."""
     opt = dict(self._render_options)
     opt.update(options)
     cam, h, w = opt.get('camera_id', 'fixedfar'), int(opt.get('height', 256)), int(opt.get('width', 256))
     if isinstance(cam, str) and cam not in nat.Context.CAMERAS:
       raise KeyError(f'unknown camera {cam!r}: one of {sorted(nat.Context.CAMERAS)}')
-    return np.concatenate(self._map(lambda c, s, e: c.render(cam, w, h, overlays=self._render_lidars_and_collision)))
+    ov = self._render_lidars_and_collision
+    if envs is None:
+      return np.concatenate(self._map(lambda c, s, e: c.render(cam, w, h, overlays=ov)))
+    ids = np.asarray(envs)
+    if ids.ndim != 1:
+      raise ValueError(f'envs: a 1-D sequence of env indices, not shape {ids.shape}')
+    if ids.size == 0:
+      return np.zeros((0, h, w, 3), np.uint8)
+    if ids.dtype.kind not in 'iu':
+      raise ValueError(f'envs: integer indices, not {ids.dtype}')
+    ids = ids.astype(np.int64)
+    if ids.min() < 0 or ids.max() >= self.n_envs:
+      raise ValueError(f'envs: index {int(ids.min() if ids.min() < 0 else ids.max())} out of range ({self.n_envs} envs)')
+    out = np.zeros((len(ids), h, w, 3), np.uint8)
+
+    def part(c, s, e):
+      sel = np.flatnonzero((ids >= s) & (ids < e))
+      if sel.size:
+        out[sel] = c.render(cam, w, h, overlays=ov, envs=(ids[sel] - s).astype(np.int32))
+    self._map(part)
+    return out
 
   def close(self):
     for c, b in zip(self._ctx, self._dev or []):
@@ -504,6 +580,7 @@ class BatchedSafeAdaptationGym:
     return np.concatenate([o[0] for o in outs]), np.concatenate([o[1] for o in outs])
 
   def set_state(self, rec_f, rec_i):
+    self._img_valid = False
     self._map(lambda c, s, e: c.set_state(rec_f[s:e], rec_i[s:e]))
 
   # -- internals ------------------------------------------------------------------------
@@ -598,14 +675,15 @@ class BatchedSafeAdaptationGym:
       rows = [c.dev_download(nat.C.c_void_p(p), (e - s,), np.uint8).astype(bool) for c, (s, e), p in zip(self._ctx, self._ranges, ptrs)]
     if self.device_buffers:
       bufs = self._dev_bufs()
-      for c, b, r, (s, e) in zip(self._ctx, bufs, rows, self._ranges):
-        if self._rgb_observation:   # the image is a function of the state: the kept envs render what the step rendered
-          c.render_rgb_device(b['img'])
+      for c, b, r, (s, e), p in zip(self._ctx, bufs, rows, self._ranges, ptrs):
+        if self._rgb_observation:   # the image is a function of the state: the kept rows hold what the step rendered
+          c.render_rows_device(nat.C.c_void_p(p) if self._img_valid else None, b['img'])
         else:
           last = c.dev_download(b['obs'], (e - s, self.robot.obs_dim), np.float32)
           last[r] = c.observe()[r]
           c.dev_upload(b['obs'], last)
       self.wait()
+      self._img_valid = self._rgb_observation
       outs = [self._views(k)[0] for k in range(len(self._ctx))]
       return outs[0] if len(outs) == 1 else outs
     new = self._render_rgb() if self._rgb_observation else np.concatenate(self._map(lambda c, s, e: c.observe()))
@@ -638,6 +716,7 @@ class BatchedSafeAdaptationGym:
           c.render_rgb_device(b['img'])
         else:
           c.dev_upload(b['obs'], c.observe())
+      self._img_valid = self._rgb_observation
       self.wait()
       outs = [self._views(k)[0] for k in range(len(self._ctx))]
       return outs[0] if len(outs) == 1 else outs
