@@ -299,6 +299,47 @@ int sag_render_rows_device(sag_ctx* ctx, int32_t camera, int32_t width, int32_t 
 int sag_render_envs(sag_ctx* ctx, int32_t camera, int32_t width, int32_t height, int32_t flags,
                     const int32_t* env_ids, int32_t n, uint8_t* out);
 
+/* Depth and segmentation images (physics.render(depth=True) / (segmentation=True) behind the reference's render_options):
+ * the same ray caster, cameras, sizes and flags as sag_render, stating per pixel the NEAREST surface of any alpha - a
+ * translucent hazard disc or goal cylinder is a surface; of two geoms at exactly one distance the earlier in the scene's
+ * build order (hazards, vases, pillars, goal, buttons, task object, robot geoms, lidar rings, cost sphere); then the floor.
+ *   SAG_RENDER_DEPTH         [rows][height][width] float: the distance from the camera plane in metres, as dm_control
+ *                            linearises the z-buffer (not the ray's length): t / sqrt(1 + u^2 + v^2) for the pixel's ray
+ *                            u X + v Y - Z, computed in double and rounded once.  Sky pixels hold SAG_DEPTH_SKY (MuJoCo's
+ *                            default zfar taken as metres: the model's extent is not known here - parity unpinned, as for
+ *                            the colour image).
+ *   SAG_RENDER_SEGMENTATION  [rows][height][width][2] int32: channel 0 the instance, channel 1 the class (enum
+ *                            sag_seg_class), mirroring dm_control's (objid, objtype); the sky is (-1, -1).
+ * Row 0 = top. */
+enum sag_render_output { SAG_RENDER_DEPTH = 1, SAG_RENDER_SEGMENTATION = 2 };
+#define SAG_DEPTH_SKY 50.0f
+enum sag_seg_class {
+  SAG_SEG_FLOOR = 0,  /* instance 0                                                                         */
+  SAG_SEG_HAZARD = 1, /* instance = the index in the record; so for VASE, PILLAR and BUTTON                 */
+  SAG_SEG_VASE = 2,
+  SAG_SEG_PILLAR = 3,
+  SAG_SEG_GOAL = 4,   /* instance 0                                                                         */
+  SAG_SEG_BUTTON = 5,
+  SAG_SEG_OBJECT = 6, /* PushBox box 0 and its corner columns 1..4 in build order; rod or ball 0            */
+  SAG_SEG_ROBOT = 7,  /* geom index in build order: Point 0 sphere, 1 arrow; Car 0..4 boxes, 5..6 wheels,   */
+                      /* 7 rear ball; Doggo 0..13 in geom-table order                                       */
+  SAG_SEG_LIDAR = 8,  /* instance = ring * 16 + bin; only with flags & 1                                    */
+  SAG_SEG_COST = 9    /* instance 0; only with flags & 1 and the cost flag up                               */
+};
+/* Device buffer, stream-ordered, no wait, no timing events.  d_mask as in sag_render_rows_device: [n_envs] device bytes,
+ * NULL = every env; env b goes into row b and rows of other envs are not written.  d_out: [n_envs] rows, aligned to 4 B
+ * (depth) or 8 B (segmentation).  d_obs / d_cost: what the overlays show (device pointers or NULL).
+ * SAG_ERR_ARG, nothing launched: an unknown output, bad camera / size, NULL or misaligned d_out. */
+int sag_render_aux_device(sag_ctx* ctx, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                          const float* d_obs, const uint8_t* d_cost, const uint8_t* d_mask, void* d_out);
+/* Host buffer: row j = env env_ids[j] (host int32, any order, duplicates allowed); env_ids == NULL: envs 0 .. n_envs - 1,
+ * n is ignored.  Overlays show the context's own observation / cost rows, as sag_render.  The staging is sized for the rows
+ * asked for and shared with sag_render / sag_render_envs.  n == 0: SAG_OK, nothing launched.
+ * SAG_ERR_ARG, nothing launched: an unknown output, bad camera / size, NULL out with rows to write, n < 0, an index outside
+ * [0, n_envs). */
+int sag_render_aux(sag_ctx* ctx, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                   const int32_t* env_ids, int32_t n, void* out);
+
 /* Diagnostic: how many envs the last split step handed to the busy kernel (0 for the
  * single-kernel form).  Synchronises the context stream. */
 int sag_busy_count(sag_ctx* ctx, int32_t* count);

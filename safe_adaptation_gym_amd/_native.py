@@ -32,7 +32,7 @@ EXPORTS = [
     'sag_robot_info', 'sag_create', 'sag_destroy', 'sag_last_error', 'sag_set_layout',
     'sag_reset', 'sag_get_state', 'sag_set_state', 'sag_step', 'sag_step_device', 'sag_wait',
     'sag_observe', 'sag_set_ext_contacts', 'sag_lidar_cost', 'sag_lidar_cost_device', 'sag_set_seed', 'sag_dev_alloc', 'sag_dev_free', 'sag_dev_upload',
-    'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_render_rows_device', 'sag_render_envs', 'sag_debug_doggo_coop',
+    'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_render_rows_device', 'sag_render_envs', 'sag_render_aux', 'sag_render_aux_device', 'sag_debug_doggo_coop',
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
     'sag_episode_clear', 'sag_fork_device', 'sag_fork_counts'
@@ -104,6 +104,8 @@ def load():
   lib.sag_render_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
   lib.sag_render_rows_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
   lib.sag_render_envs.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, C.POINTER(C.c_uint8)]
+  lib.sag_render_aux_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
+  lib.sag_render_aux.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, vp]
   lib.sag_debug_doggo_coop.argtypes = [vp, C.POINTER(C.c_double)]
   lib.sag_debug_cycles.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.c_int32]
   lib.sag_world_config_default.argtypes = [C.POINTER(WorldConfig)]
@@ -535,13 +537,22 @@ class Context:
     return img
 
   CAMERAS = {'vision': 0, 'fixednear': 1, 'fixedfar': 2, 'track': 3}
+  OUTPUTS = {'depth': 1, 'segmentation': 2}   # enum sag_render_output
+  DEPTH_SKY = 50.0                            # SAG_DEPTH_SKY: what a sky pixel of the depth image holds
 
-  def render(self, camera='fixedfar', width=256, height=256, overlays=True, envs=None):
+  def render(self, camera='fixedfar', width=256, height=256, overlays=True, envs=None, output='rgb'):
     """[n_envs, height, width, 3] uint8 from one of the scene's cameras (name or id), optionally with the lidar
     rings and the cost indicator of the last step.  envs: int32 indices of the envs to render, any order, duplicates
     allowed (sag_render_envs) -> [len(envs), height, width, 3], row j = env envs[j]; device work and staging are for
-    len(envs) images only."""
+    len(envs) images only.
+    output: 'rgb'; 'depth' -> [rows, height, width] float32, the distance of the nearest surface from the camera plane in
+    metres (sky: DEPTH_SKY); 'segmentation' -> [rows, height, width, 2] int32, (instance, class) of that surface (enum
+    sag_seg_class; sky (-1, -1)) (sag_render_aux)."""
     cam = self.CAMERAS[camera] if isinstance(camera, str) else int(camera)
+    if output != 'rgb':
+      if output not in self.OUTPUTS:
+        raise ValueError(f'output: one of {["rgb"] + sorted(self.OUTPUTS)}, not {output!r}')
+      return self._render_aux(self.OUTPUTS[output], cam, int(width), int(height), overlays, envs)
     if envs is not None:
       ids = np.asarray(envs)
       if ids.ndim != 1 or (ids.size and ids.dtype.kind not in 'iu'):
@@ -557,6 +568,34 @@ class Context:
     self._check(self.lib.sag_render(self.h, cam, int(width), int(height), 1 if overlays else 0,
                                     img.ctypes.data_as(C.POINTER(C.c_uint8))), 'sag_render')
     return img
+
+  def _render_aux(self, output, cam, width, height, overlays, envs):
+    ids, rows = None, self.n_envs
+    if envs is not None:
+      ids = np.asarray(envs)
+      if ids.ndim != 1 or (ids.size and ids.dtype.kind not in 'iu'):
+        raise ValueError(f'envs: a 1-D sequence of integer indices, not {ids.dtype} {ids.shape}')
+      if ids.size and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31):   # (must not wrap into range; the library checks the rest)
+        raise SagError(f'sag_render_aux: an env index outside int32 ({self.n_envs} envs)')
+      ids, rows = np.ascontiguousarray(ids, np.int32), len(ids)
+    img = np.zeros((rows, height, width) if output == self.OUTPUTS['depth'] else (rows, height, width, 2),
+                   np.float32 if output == self.OUTPUTS['depth'] else np.int32)
+    if ids is not None and rows == 0:
+      return img   # (an empty list is not NULL, which would mean every env)
+    self._check(self.lib.sag_render_aux(self.h, output, cam, width, height, 1 if overlays else 0,
+                                        None if ids is None else _ptr(ids, C.c_int32), rows, img.ctypes.data_as(C.c_void_p)),
+                'sag_render_aux')
+    return img
+
+  def render_aux_device(self, output, d_out, d_mask=None, camera='vision', width=64, height=64, overlays=False, d_obs=None, d_cost=None):
+    """sag_render_aux_device: the 'depth' ([n_envs][height][width] float32, d_out aligned to 4 bytes) or 'segmentation'
+    ([n_envs][height][width][2] int32, aligned to 8) images of the envs with a non-zero byte of d_mask (device pointer of
+    [n_envs] bytes; None: every env) into their own rows of d_out, enqueued on the context stream; the other rows are not
+    written.  d_obs / d_cost: what the overlays show (device pointers or None)."""
+    cam = self.CAMERAS[camera] if isinstance(camera, str) else int(camera)
+    out = self.OUTPUTS[output] if isinstance(output, str) else int(output)
+    self._check(self.lib.sag_render_aux_device(self.h, out, cam, int(width), int(height), 1 if overlays else 0, d_obs, d_cost,
+                                               d_mask, d_out), 'sag_render_aux_device')
 
   def render_rows_device(self, d_mask, d_out, camera='vision', width=64, height=64, overlays=False, d_obs=None, d_cost=None):
     """sag_render_rows_device: the images of the envs with a non-zero byte of d_mask (device pointer of [n_envs] bytes; None:

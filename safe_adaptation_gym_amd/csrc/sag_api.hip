@@ -1328,6 +1328,64 @@ int sag_render_envs(sag_ctx* c, int32_t camera, int32_t width, int32_t height, i
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SAG_OK;
 }
+// depth / segmentation (sag_render.hpp r_render_env<OUT>): bytes per pixel = the alignment of the image, 0 for an unknown output
+static size_t aux_pixel_bytes(int32_t output) {
+  return output == SAG_RENDER_DEPTH ? sizeof(float) : (output == SAG_RENDER_SEGMENTATION ? 2 * sizeof(int32_t) : 0);
+}
+static int aux_args_ok(sag_ctx* c, const char* who, int32_t output, int32_t camera, int32_t width, int32_t height) {
+  if (!aux_pixel_bytes(output)) return fail(c, SAG_ERR_ARG, "%s: unknown output %d", who, output);
+  return render_args_ok(c, camera, width, height);
+}
+// masked (d_ids == nullptr; d_mask == nullptr: every env) or listed launch of `rows` workgroups
+static void aux_launch(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
+                       const uint8_t* d_cost, const uint8_t* d_mask, const int32_t* d_ids, int rows, void* d_out) {
+#define SAG_AUX_LAUNCH(KERNEL, SEL)                                                                                              \
+  hipLaunchKernelGGL(KERNEL, dim3(rows), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height, flags, \
+                     d_obs, c->rb.obs_dim, d_cost, SEL, d_out)
+  if (d_ids) {
+    if (output == SAG_RENDER_DEPTH) SAG_AUX_LAUNCH((k_render_aux_list<R_OUT_DEPTH>), d_ids);
+    else SAG_AUX_LAUNCH((k_render_aux_list<R_OUT_SEG>), d_ids);
+  } else {
+    if (output == SAG_RENDER_DEPTH) SAG_AUX_LAUNCH((k_render_aux_rows<R_OUT_DEPTH>), d_mask);
+    else SAG_AUX_LAUNCH((k_render_aux_rows<R_OUT_SEG>), d_mask);
+  }
+#undef SAG_AUX_LAUNCH
+}
+int sag_render_aux_device(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                          const float* d_obs, const uint8_t* d_cost, const uint8_t* d_mask, void* d_out) {
+  if (!c || !d_out) return c ? fail(c, SAG_ERR_ARG, "sag_render_aux_device: null argument") : SAG_ERR_ARG;
+  if (int rc = aux_args_ok(c, "sag_render_aux_device", output, camera, width, height)) return rc;
+  if (reinterpret_cast<uintptr_t>(d_out) % aux_pixel_bytes(output))
+    return fail(c, SAG_ERR_ARG, "sag_render_aux_device: d_out is not aligned to %d bytes", (int)aux_pixel_bytes(output));
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  aux_launch(c, output, camera, width, height, flags, d_obs, d_cost, d_mask, nullptr, c->N, d_out);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+// host buffer: the staging (d_rgb, grown through ensure_rgb so that rgb_bytes stays true for the next RGB call) holds the
+// index list, rounded up to 16 bytes, in front of the rows asked for; no list for env_ids == NULL (every env, masked form)
+int sag_render_aux(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags, const int32_t* env_ids,
+                   int32_t n, void* out) {
+  if (!c) return SAG_ERR_ARG;
+  if (int rc = aux_args_ok(c, "sag_render_aux", output, camera, width, height)) return rc;
+  if (!env_ids) n = c->N;
+  if (n < 0 || (n > 0 && !out)) return fail(c, SAG_ERR_ARG, "sag_render_aux: n %d or a null argument", n);
+  for (int32_t j = 0; env_ids && j < n; j++)
+    if (env_ids[j] < 0 || env_ids[j] >= c->N) return fail(c, SAG_ERR_ARG, "sag_render_aux: env %d (entry %d) of %d envs", env_ids[j], j, c->N);
+  if (n == 0) return SAG_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t list = env_ids ? ((size_t)n * sizeof(int32_t) + 15) & ~(size_t)15 : 0;
+  const size_t bytes = (size_t)n * width * height * aux_pixel_bytes(output);
+  if (int rc = ensure_rgb(c, list + bytes)) return rc;
+  // (the stream is joined below: env_ids has been read when the call returns)
+  if (env_ids) HIPCHK(c, hipMemcpyAsync(c->d_rgb, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+  aux_launch(c, output, camera, width, height, flags, (const float*)c->d_obs, (const uint8_t*)c->d_cost, nullptr,
+             env_ids ? reinterpret_cast<const int32_t*>(c->d_rgb) : nullptr, n, c->d_rgb + list);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->d_rgb + list, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return SAG_OK;
+}
 // rgb_observation: the 64 x 64 image of the robot's own camera, no overlays
 int sag_render_rgb_device(sag_ctx* c, void* d_out) { return sag_render_device(c, SAG_CAM_VISION, R_W, R_H, 0, nullptr, nullptr, d_out); }
 int sag_render_rgb(sag_ctx* c, uint8_t* out) { return sag_render(c, SAG_CAM_VISION, R_W, R_H, 0, out); }

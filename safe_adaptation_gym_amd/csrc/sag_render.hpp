@@ -26,6 +26,10 @@ struct RCam { double o[3], X[3], Y[3], Z[3], tanh_; };
 // 3 rod: cylinder (b = 0) or capsule (b = 1) of radius a from c to e (any orientation: wheels, the Doggo's limbs)
 struct RObj { int kind; double c[3], a, b, h, cs, sn, rgb[3], alpha, e[3]; };
 constexpr int R_MAXOBJ = 112, R_W = 64, R_H = 64, R_MAXLAYERS = 12;
+// what a workgroup writes per pixel (r_render_env<OUT>): the colour, or one of the auxiliary images of enum sag_render_output
+enum { R_OUT_RGB = 0, R_OUT_DEPTH = SAG_RENDER_DEPTH, R_OUT_SEG = SAG_RENDER_SEGMENTATION };
+struct RSeg { int16_t inst, cls; };   // (instance, enum sag_seg_class) of a geom
+struct alignas(8) RSegPixel { int32_t inst, cls; };   // a pixel of the segmentation image: one 8-byte store
 
 __device__ inline void r_norm(double* v) {
   const double n = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
@@ -200,9 +204,18 @@ __device__ inline void r_rod(RObj* ob, int& n, const double* R, const double* p,
   q.rgb[0] = cr; q.rgb[1] = cg; q.rgb[2] = cb; q.alpha = al;
 }
 
-// One workgroup renders env i into image `row` of out ([rows][H][W][3] uint8): the body of the three kernels below, which
+// (instance, class) of the geoms in build order: LDS of the segmentation kernels alone (no other kernel reaches this function)
+__device__ __forceinline__ RSeg* r_segtab() {
+  __shared__ RSeg tab[R_MAXOBJ];
+  return tab;
+}
+
+// One workgroup renders env i into image `row` of out ([rows][H][W][3] uint8): the body of the kernels below, which
 // differ only in how a workgroup finds its env and its row.  obs / cost (device pointers or nullptr): last observation
 // [N][obs_dim] and cost flags for the overlays (lidar rings, cost indicator), read at row i - they follow the env.
+// OUT: R_OUT_RGB the colour image; R_OUT_DEPTH ([rows][H][W] float, `out` aligned to 4) and R_OUT_SEG ([rows][H][W][2]
+// int32, aligned to 8) the NEAREST surface of any alpha - same scene, same cull, same rays; no shading, no layer list.
+template <int OUT>
 __device__ __forceinline__ void r_render_env(const float* __restrict__ S, const int32_t* __restrict__ I, int N, int robot,
                                              int cam_id, int W, int H, int flags, const float* __restrict__ obs, int obs_dim,
                                              const uint8_t* __restrict__ cost, uint8_t* __restrict__ out, const size_t i,
@@ -302,6 +315,26 @@ __device__ __forceinline__ void r_render_env(const float* __restrict__ S, const 
       }
       if (cost && cost[i]) r_obj(ob, n, 2, p[0], p[1], p[2], 0.25, 0, 0, 0.0, 1, 0, 0, 0.5);
     }
+    if constexpr (OUT == R_OUT_SEG) {
+      // the build order above is fixed - hazards, vases, pillars, goal, buttons, task object, robot, rings, cost sphere - so the
+      // counts give every geom its class and its instance within the class
+      RSeg* sg = r_segtab();
+      int k = 0;
+      auto put = [&](int cnt, int cls, int first) {
+        for (int j = 0; j < cnt && k < n; j++, k++) { sg[k].inst = (int16_t)(first + j); sg[k].cls = (int16_t)cls; }
+      };
+      put(nH, SAG_SEG_HAZARD, 0);
+      put(nV, SAG_SEG_VASE, 0);
+      put(nP, SAG_SEG_PILLAR, 0);
+      put(goal_body ? 1 : 0, SAG_SEG_GOAL, 0);
+      put(nB, SAG_SEG_BUTTON, 0);
+      put(box_kind == SAG_BOX_BOX ? 5 : (box_kind == SAG_BOX_ROD || box_kind == SAG_BOX_BALL ? 1 : 0), SAG_SEG_OBJECT, 0);
+      put(robot == SAG_ROBOT_POINT ? 2 : (robot == SAG_ROBOT_CAR ? 8 : DG_NGEOM), SAG_SEG_ROBOT, 0);
+      if (flags & SAG_RENDER_OVERLAYS) {
+        put(3 * SAG_LIDAR_BINS, SAG_SEG_LIDAR, 0);   // instance = ring * 16 + bin
+        put(cost && cost[i] ? 1 : 0, SAG_SEG_COST, 0);
+      }
+    }
     nob_s = n;
   }
   __syncthreads();
@@ -344,6 +377,33 @@ __device__ __forceinline__ void r_render_env(const float* __restrict__ S, const 
     for (int k = 0; k < 3; k++) d[k] = u * cam.X[k] + v * cam.Y[k] - cam.Z[k];
     r_norm(d);
     const float fx = (float)d[0], fy = (float)d[1], fz = (float)d[2];
+    if constexpr (OUT != R_OUT_RGB) {
+      // one pass in geom order over the geoms that pass the cull: the smallest t and its geom, whatever the geom's alpha (a
+      // translucent disc is a surface); the strict < keeps the earlier geom on an exact tie.  Then the floor, as below.
+      double best = 1e30, t;
+      int kb = -1;   // the geom; -1 sky, -2 floor
+#pragma unroll 1
+      for (int k = 0; k < nob; k++) {
+        double n[3];
+        if (!may_hit(k, fx, fy, fz) || !r_hit(ob[k], cam.o, d, t, n)) continue;
+        if (t < best) { best = t; kb = k; }
+      }
+      if (d[2] < 0) {
+        const double tf = -cam.o[2] / d[2], fx = cam.o[0] + tf * d[0], fy = cam.o[1] + tf * d[1];
+        if (tf > 1e-6 && tf < best && fabs(fx) <= 3.5 && fabs(fy) <= 3.5) { best = tf; kb = -2; }
+      }
+      const size_t at = row * (size_t)W * H + px;
+      if constexpr (OUT == R_OUT_DEPTH) {
+        // distance from the camera plane (how dm_control linearises the z-buffer), not the ray's length: the ray u X + v Y - Z
+        // advances 1 along the viewing direction per sqrt(1 + u^2 + v^2) of length.  fp64, rounded once.
+        reinterpret_cast<float*>(out)[at] = kb == -1 ? SAG_DEPTH_SKY : (float)(best / sqrt(1.0 + u * u + v * v));
+      } else {
+        const RSeg* sg = r_segtab();
+        reinterpret_cast<RSegPixel*>(out)[at] = kb >= 0 ? RSegPixel{sg[kb].inst, sg[kb].cls}
+                                                        : (kb == -2 ? RSegPixel{0, SAG_SEG_FLOOR} : RSegPixel{-1, -1});
+      }
+      continue;   // (what follows is the colour image's code, which the auxiliary instantiations never reach)
+    }
     double best = 1e30, col[3] = {0, 0, 0}, t;
     bool hit = false;
     // ONE pass over the geoms (sphere test and intersection once each): an opaque hit moves the surface in; a translucent hit goes into
@@ -397,7 +457,7 @@ __global__ __launch_bounds__(256) void k_render_rgb(const float* __restrict__ S,
                                                     int robot, int cam_id, int W, int H, int flags,
                                                     const float* __restrict__ obs, int obs_dim,
                                                     const uint8_t* __restrict__ cost, uint8_t* __restrict__ out) {
-  r_render_env(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, blockIdx.x, blockIdx.x);
+  r_render_env<R_OUT_RGB>(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, blockIdx.x, blockIdx.x);
 }
 
 // masked, in place: the envs with a non-zero byte of mask [N], env b into row b; the other rows of out are not touched.
@@ -409,7 +469,7 @@ __global__ __launch_bounds__(256) void k_render_rows(const float* __restrict__ S
                                                      const uint8_t* __restrict__ cost, const uint8_t* __restrict__ mask,
                                                      uint8_t* __restrict__ out) {
   if (!mask[blockIdx.x]) return;
-  r_render_env(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, blockIdx.x, blockIdx.x);
+  r_render_env<R_OUT_RGB>(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, blockIdx.x, blockIdx.x);
 }
 
 // listed, compact: workgroup j renders env ids[j] into row j.  out: [n][H][W][3], n = the grid; duplicates are fine (rows
@@ -421,7 +481,32 @@ __global__ __launch_bounds__(256) void k_render_list(const float* __restrict__ S
                                                      uint8_t* __restrict__ out) {
   const int32_t e = ids[blockIdx.x];
   if (e < 0 || e >= N) return;
-  r_render_env(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, (size_t)e, blockIdx.x);
+  r_render_env<R_OUT_RGB>(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, out, (size_t)e, blockIdx.x);
+}
+
+// The auxiliary images (OUT = R_OUT_DEPTH: out [rows][H][W] float; R_OUT_SEG: [rows][H][W][2] int32), one masked and one
+// listed form.  Masked, in place, as k_render_rows: env b into row b; mask == nullptr is every env; an unselected workgroup
+// reads its byte and leaves before the first barrier.
+template <int OUT>
+__global__ __launch_bounds__(256) void k_render_aux_rows(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
+                                                         int robot, int cam_id, int W, int H, int flags,
+                                                         const float* __restrict__ obs, int obs_dim,
+                                                         const uint8_t* __restrict__ cost, const uint8_t* __restrict__ mask,
+                                                         void* __restrict__ out) {
+  if (mask && !mask[blockIdx.x]) return;
+  r_render_env<OUT>(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, static_cast<uint8_t*>(out), blockIdx.x, blockIdx.x);
+}
+
+// listed, compact, as k_render_list: workgroup j renders env ids[j] into row j
+template <int OUT>
+__global__ __launch_bounds__(256) void k_render_aux_list(const float* __restrict__ S, const int32_t* __restrict__ I, int N,
+                                                         int robot, int cam_id, int W, int H, int flags,
+                                                         const float* __restrict__ obs, int obs_dim,
+                                                         const uint8_t* __restrict__ cost, const int32_t* __restrict__ ids,
+                                                         void* __restrict__ out) {
+  const int32_t e = ids[blockIdx.x];
+  if (e < 0 || e >= N) return;
+  r_render_env<OUT>(S, I, N, robot, cam_id, W, H, flags, obs, obs_dim, cost, static_cast<uint8_t*>(out), (size_t)e, blockIdx.x);
 }
 
 }  // namespace sag

@@ -530,31 +530,40 @@ class BatchedSafeAdaptationGym:
     envs: a 1-D integer sequence of global env indices, any order, duplicates allowed -> [len(envs), height, width, 3] in
     that order (sag_render_envs).  Only these envs are ray-cast, staged and copied: each shard renders its own entries and
     a shard with none launches nothing.  ValueError, before anything is launched, for an index outside [0, n_envs), a
-    dtype that is not an integer (bool included) and an array that is not 1-D."""
+    dtype that is not an integer (bool included) and an array that is not 1-D.
+
+    depth=True -> [N, height, width] float32: the distance of the nearest surface (translucent ones included) from the
+    camera plane in metres; sky pixels hold 50.0 (Context.DEPTH_SKY).  segmentation=True -> [N, height, width, 2] int32:
+    (instance, class) of that surface, mirroring dm_control's (objid, objtype) with the classes of include/sag.h enum
+    sag_seg_class; the sky is (-1, -1).  Both true: ValueError, as dm_control, before anything is launched."""
     opt = dict(self._render_options)
     opt.update(options)
     cam, h, w = opt.get('camera_id', 'fixedfar'), int(opt.get('height', 256)), int(opt.get('width', 256))
     if isinstance(cam, str) and cam not in nat.Context.CAMERAS:
       raise KeyError(f'unknown camera {cam!r}: one of {sorted(nat.Context.CAMERAS)}')
+    if opt.get('depth') and opt.get('segmentation'):
+      raise ValueError('render: depth and segmentation are mutually exclusive')
+    output = 'depth' if opt.get('depth') else ('segmentation' if opt.get('segmentation') else 'rgb')
+    tail, dtype = {'rgb': ((3,), np.uint8), 'depth': ((), np.float32), 'segmentation': ((2,), np.int32)}[output]
     ov = self._render_lidars_and_collision
     if envs is None:
-      return np.concatenate(self._map(lambda c, s, e: c.render(cam, w, h, overlays=ov)))
+      return np.concatenate(self._map(lambda c, s, e: c.render(cam, w, h, overlays=ov, output=output)))
     ids = np.asarray(envs)
     if ids.ndim != 1:
       raise ValueError(f'envs: a 1-D sequence of env indices, not shape {ids.shape}')
     if ids.size == 0:
-      return np.zeros((0, h, w, 3), np.uint8)
+      return np.zeros((0, h, w) + tail, dtype)
     if ids.dtype.kind not in 'iu':
       raise ValueError(f'envs: integer indices, not {ids.dtype}')
     ids = ids.astype(np.int64)
     if ids.min() < 0 or ids.max() >= self.n_envs:
       raise ValueError(f'envs: index {int(ids.min() if ids.min() < 0 else ids.max())} out of range ({self.n_envs} envs)')
-    out = np.zeros((len(ids), h, w, 3), np.uint8)
+    out = np.zeros((len(ids), h, w) + tail, dtype)
 
     def part(c, s, e):
       sel = np.flatnonzero((ids >= s) & (ids < e))
       if sel.size:
-        out[sel] = c.render(cam, w, h, overlays=ov, envs=(ids[sel] - s).astype(np.int32))
+        out[sel] = c.render(cam, w, h, overlays=ov, envs=(ids[sel] - s).astype(np.int32), output=output)
     self._map(part)
     return out
 
