@@ -540,6 +540,17 @@ class Context:
   OUTPUTS = {'depth': 1, 'segmentation': 2}   # enum sag_render_output
   DEPTH_SKY = 50.0                            # SAG_DEPTH_SKY: what a sky pixel of the depth image holds
 
+  def _env_ids(self, envs, who):
+    """envs of render(): None, or the indices as a contiguous int32 array (the library checks them against n_envs)."""
+    if envs is None:
+      return None
+    ids = np.asarray(envs)
+    if ids.ndim != 1 or (ids.size and ids.dtype.kind not in 'iu'):
+      raise ValueError(f'envs: a 1-D sequence of integer indices, not {ids.dtype} {ids.shape}')
+    if ids.size and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31):   # (must not wrap into range; the library checks the rest)
+      raise SagError(f'{who}: an env index outside int32 ({self.n_envs} envs)')
+    return np.ascontiguousarray(ids, np.int32)
+
   def render(self, camera='fixedfar', width=256, height=256, overlays=True, envs=None, output='rgb'):
     """[n_envs, height, width, 3] uint8 from one of the scene's cameras (name or id), optionally with the lidar
     rings and the cost indicator of the last step.  envs: int32 indices of the envs to render, any order, duplicates
@@ -549,42 +560,21 @@ class Context:
     metres (sky: DEPTH_SKY); 'segmentation' -> [rows, height, width, 2] int32, (instance, class) of that surface (enum
     sag_seg_class; sky (-1, -1)) (sag_render_aux)."""
     cam = self.CAMERAS[camera] if isinstance(camera, str) else int(camera)
-    if output != 'rgb':
-      if output not in self.OUTPUTS:
-        raise ValueError(f'output: one of {["rgb"] + sorted(self.OUTPUTS)}, not {output!r}')
-      return self._render_aux(self.OUTPUTS[output], cam, int(width), int(height), overlays, envs)
-    if envs is not None:
-      ids = np.asarray(envs)
-      if ids.ndim != 1 or (ids.size and ids.dtype.kind not in 'iu'):
-        raise ValueError(f'envs: a 1-D sequence of integer indices, not {ids.dtype} {ids.shape}')
-      if ids.size and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31):   # (must not wrap into range; the library checks the rest)
-        raise SagError(f'sag_render_envs: an env index outside int32 ({self.n_envs} envs)')
-      ids = np.ascontiguousarray(ids, np.int32)
-      img = np.zeros((len(ids), int(height), int(width), 3), np.uint8)
-      self._check(self.lib.sag_render_envs(self.h, cam, int(width), int(height), 1 if overlays else 0, _ptr(ids, C.c_int32),
-                                           len(ids), img.ctypes.data_as(C.POINTER(C.c_uint8))), 'sag_render_envs')
-      return img
-    img = np.zeros((self.n_envs, int(height), int(width), 3), np.uint8)
-    self._check(self.lib.sag_render(self.h, cam, int(width), int(height), 1 if overlays else 0,
-                                    img.ctypes.data_as(C.POINTER(C.c_uint8))), 'sag_render')
-    return img
-
-  def _render_aux(self, output, cam, width, height, overlays, envs):
-    ids, rows = None, self.n_envs
-    if envs is not None:
-      ids = np.asarray(envs)
-      if ids.ndim != 1 or (ids.size and ids.dtype.kind not in 'iu'):
-        raise ValueError(f'envs: a 1-D sequence of integer indices, not {ids.dtype} {ids.shape}')
-      if ids.size and (int(ids.min()) < -2**31 or int(ids.max()) >= 2**31):   # (must not wrap into range; the library checks the rest)
-        raise SagError(f'sag_render_aux: an env index outside int32 ({self.n_envs} envs)')
-      ids, rows = np.ascontiguousarray(ids, np.int32), len(ids)
-    img = np.zeros((rows, height, width) if output == self.OUTPUTS['depth'] else (rows, height, width, 2),
-                   np.float32 if output == self.OUTPUTS['depth'] else np.int32)
-    if ids is not None and rows == 0:
-      return img   # (an empty list is not NULL, which would mean every env)
-    self._check(self.lib.sag_render_aux(self.h, output, cam, width, height, 1 if overlays else 0,
-                                        None if ids is None else _ptr(ids, C.c_int32), rows, img.ctypes.data_as(C.c_void_p)),
-                'sag_render_aux')
+    if output != 'rgb' and output not in self.OUTPUTS:
+      raise ValueError(f'output: one of {["rgb"] + sorted(self.OUTPUTS)}, not {output!r}')
+    out = self.OUTPUTS.get(output, 0)
+    who = 'sag_render_aux' if out else ('sag_render' if envs is None else 'sag_render_envs')
+    ids = self._env_ids(envs, who)
+    rows = self.n_envs if ids is None else len(ids)
+    pixel, dtype = (((3,), np.uint8), ((), np.float32), ((2,), np.int32))[out]
+    img = np.zeros((rows, int(height), int(width)) + pixel, dtype)
+    args = (cam, int(width), int(height), 1 if overlays else 0)
+    p, idp = _ptr(img, C.c_uint8), _ptr(ids, C.c_int32)
+    if out:
+      rc = self.lib.sag_render_aux(self.h, out, *args, idp, rows, p) if rows else 0   # (an empty list is not NULL, which would mean every env)
+    else:
+      rc = self.lib.sag_render(self.h, *args, p) if ids is None else self.lib.sag_render_envs(self.h, *args, idp, rows, p)
+    self._check(rc, who)
     return img
 
   def render_aux_device(self, output, d_out, d_mask=None, camera='vision', width=64, height=64, overlays=False, d_obs=None, d_cost=None):

@@ -1254,14 +1254,42 @@ int sag_debug_doggo_coop(sag_ctx* c, double* out) {
   return SAG_OK;
 }
 
-// images of every env at its current state, ray-cast on the device (sag_render.hpp): [n_envs][height][width][3] uint8.
-// d_obs / d_cost: the observation and cost flags the overlays show (device pointers or NULL)
-static int render_args_ok(sag_ctx* c, int32_t camera, int32_t width, int32_t height) {
+// Images of the envs at their current state, ray-cast on the device (sag_render.hpp).  output: 0 the colour image
+// [rows][height][width][3] uint8, or one of enum sag_render_output.  -> bytes per pixel, 0 for an unknown output
+static size_t render_pixel_bytes(int32_t output) {
+  return output == R_OUT_RGB ? 3 : output == SAG_RENDER_DEPTH ? sizeof(float) : output == SAG_RENDER_SEGMENTATION ? sizeof(RSegPixel) : 0;
+}
+static int render_args_ok(sag_ctx* c, const char* who, int32_t output, int32_t camera, int32_t width, int32_t height) {
+  if (!render_pixel_bytes(output)) return fail(c, SAG_ERR_ARG, "%s: unknown output %d", who, output);
   if (camera < 0 || camera > SAG_CAM_TRACK || width <= 0 || height <= 0 || width > 4096 || height > 4096)
-    return fail(c, SAG_ERR_ARG, "bad camera %d or image size %d x %d", camera, width, height);
+    return fail(c, SAG_ERR_ARG, "%s: bad camera %d or image size %d x %d", who, camera, width, height);
   return SAG_OK;
 }
-// the staging buffer of sag_render / sag_render_envs holds at least `bytes`; rgb_bytes is what d_rgb really has
+extern "C++" template <int OUT>   // (this file's functions are extern "C")
+void render_launch_as(sag_ctx* c, const RenderArgs& a, const uint8_t* d_mask, const int32_t* d_ids, int rows) {
+  if (d_ids) hipLaunchKernelGGL(k_render_list<OUT>, dim3(rows), dim3(256), 0, c->stream, a, d_ids);
+  else hipLaunchKernelGGL(k_render_rows<OUT>, dim3(rows), dim3(256), 0, c->stream, a, d_mask);
+}
+// One launch, stream-ordered, no wait: `rows` workgroups, listed (d_ids: workgroup j renders env d_ids[j] into row j) or
+// masked in place (d_mask; NULL: every env, rows = n_envs).  d_obs / d_cost: the observation and cost flags the overlays show
+// (device pointers or NULL).  d_out: aligned to its pixel, 4 B depth / 8 B segmentation.  A refused call launches nothing.
+static int render_launch(sag_ctx* c, const char* who, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                         const float* d_obs, const uint8_t* d_cost, const uint8_t* d_mask, const int32_t* d_ids, int rows, void* d_out) {
+  if (!c) return SAG_ERR_ARG;
+  if (int rc = render_args_ok(c, who, output, camera, width, height)) return rc;
+  if (!d_out) return fail(c, SAG_ERR_ARG, "%s: null argument", who);
+  if (output != R_OUT_RGB && reinterpret_cast<uintptr_t>(d_out) % render_pixel_bytes(output))
+    return fail(c, SAG_ERR_ARG, "%s: d_out is not aligned to %d bytes", who, (int)render_pixel_bytes(output));
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const RenderArgs a = {c->S, c->I, c->N, c->cfg.robot, camera, width, height, flags, d_obs, c->rb.obs_dim, d_cost, d_out};
+  if (output == SAG_RENDER_DEPTH) render_launch_as<R_OUT_DEPTH>(c, a, d_mask, d_ids, rows);
+  else if (output == SAG_RENDER_SEGMENTATION) render_launch_as<R_OUT_SEG>(c, a, d_mask, d_ids, rows);
+  else if (d_ids || d_mask) render_launch_as<R_OUT_RGB>(c, a, d_mask, d_ids, rows);
+  else hipLaunchKernelGGL(k_render_rgb, dim3(rows), dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+// the staging buffer of render_to_host holds at least `bytes`; rgb_bytes is what d_rgb really has
 static int ensure_rgb(sag_ctx* c, size_t bytes) {
   if (c->rgb_bytes >= bytes) return 0;
   if (c->d_rgb) (void)hipFree(c->d_rgb);
@@ -1270,121 +1298,63 @@ static int ensure_rgb(sag_ctx* c, size_t bytes) {
   c->rgb_bytes = bytes;
   return 0;
 }
-int sag_render_device(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
-                      const uint8_t* d_cost, void* d_out) {
-  if (!c || !d_out) return c ? fail(c, SAG_ERR_ARG, "null argument") : SAG_ERR_ARG;
-  if (int rc = render_args_ok(c, camera, width, height)) return rc;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipLaunchKernelGGL(k_render_rgb, dim3(c->N), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height,
-                     flags, d_obs, c->rb.obs_dim, d_cost, (uint8_t*)d_out);
-  HIPCHK(c, hipGetLastError());
-  return SAG_OK;
-}
-// the envs of a device mask, each into its own row: the grid is sized for n_envs whatever the mask holds, and a workgroup
-// whose byte is zero returns at once (k_render_rows) - nothing the host decides, so it follows a reset on the stream
-int sag_render_rows_device(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
-                           const uint8_t* d_cost, const uint8_t* d_mask, void* d_out) {
-  if (!d_mask) return sag_render_device(c, camera, width, height, flags, d_obs, d_cost, d_out);
-  if (!c || !d_out) return c ? fail(c, SAG_ERR_ARG, "null argument") : SAG_ERR_ARG;
-  if (int rc = render_args_ok(c, camera, width, height)) return rc;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  hipLaunchKernelGGL(k_render_rows, dim3(c->N), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height,
-                     flags, d_obs, c->rb.obs_dim, d_cost, d_mask, (uint8_t*)d_out);
-  HIPCHK(c, hipGetLastError());
-  return SAG_OK;
-}
-int sag_render(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, uint8_t* out) {
-  if (!c || !out) return c ? fail(c, SAG_ERR_ARG, "null argument") : SAG_ERR_ARG;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const size_t bytes = (size_t)c->N * (size_t)(width > 0 ? width : 0) * (size_t)(height > 0 ? height : 0) * 3;
-  if (int rc = ensure_rgb(c, bytes)) return rc;
-  // the overlays show what the last host-buffer step / observe left in the context's output buffers
-  int rc = sag_render_device(c, camera, width, height, flags, c->d_obs, c->d_cost, c->d_rgb);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(out, c->d_rgb, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SAG_OK;
-}
-// n listed envs, compact: the staging buffer holds the index list (4 n bytes, rounded up to 16) in front of the n images,
-// grown through ensure_rgb like sag_render's, so that rgb_bytes stays the size of what d_rgb points to
-int sag_render_envs(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const int32_t* env_ids, int32_t n,
-                    uint8_t* out) {
+// Into a host buffer, joined: row j = env env_ids[j] of n listed envs, or (env_ids == NULL, n = n_envs) every env.  The
+// staging buffer holds the index list (4 n bytes, rounded up to 16) in front of the n images, so it is sized for the rows asked
+// for.  The overlays show what the last host-buffer step / observe left in the context's output buffers.
+static int render_to_host(sag_ctx* c, const char* who, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                          const int32_t* env_ids, int32_t n, void* out) {
   if (!c) return SAG_ERR_ARG;
-  if (n < 0 || (n > 0 && (!env_ids || !out))) return fail(c, SAG_ERR_ARG, "sag_render_envs: n %d or a null argument", n);
-  if (int rc = render_args_ok(c, camera, width, height)) return rc;
-  for (int32_t j = 0; j < n; j++)
-    if (env_ids[j] < 0 || env_ids[j] >= c->N) return fail(c, SAG_ERR_ARG, "sag_render_envs: env %d (entry %d) of %d envs", env_ids[j], j, c->N);
-  if (n == 0) return SAG_OK;
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  const size_t list = ((size_t)n * sizeof(int32_t) + 15) & ~(size_t)15, bytes = (size_t)n * width * height * 3;
-  if (int rc = ensure_rgb(c, list + bytes)) return rc;
-  // (the stream is joined below: env_ids has been read when the call returns)
-  HIPCHK(c, hipMemcpyAsync(c->d_rgb, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_render_list, dim3(n), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height, flags,
-                     (const float*)c->d_obs, c->rb.obs_dim, (const uint8_t*)c->d_cost, reinterpret_cast<const int32_t*>(c->d_rgb),
-                     c->d_rgb + list);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(out, c->d_rgb + list, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return SAG_OK;
-}
-// depth / segmentation (sag_render.hpp r_render_env<OUT>): bytes per pixel = the alignment of the image, 0 for an unknown output
-static size_t aux_pixel_bytes(int32_t output) {
-  return output == SAG_RENDER_DEPTH ? sizeof(float) : (output == SAG_RENDER_SEGMENTATION ? 2 * sizeof(int32_t) : 0);
-}
-static int aux_args_ok(sag_ctx* c, const char* who, int32_t output, int32_t camera, int32_t width, int32_t height) {
-  if (!aux_pixel_bytes(output)) return fail(c, SAG_ERR_ARG, "%s: unknown output %d", who, output);
-  return render_args_ok(c, camera, width, height);
-}
-// masked (d_ids == nullptr; d_mask == nullptr: every env) or listed launch of `rows` workgroups
-static void aux_launch(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
-                       const uint8_t* d_cost, const uint8_t* d_mask, const int32_t* d_ids, int rows, void* d_out) {
-#define SAG_AUX_LAUNCH(KERNEL, SEL)                                                                                              \
-  hipLaunchKernelGGL(KERNEL, dim3(rows), dim3(256), 0, c->stream, c->S, c->I, c->N, c->cfg.robot, camera, width, height, flags, \
-                     d_obs, c->rb.obs_dim, d_cost, SEL, d_out)
-  if (d_ids) {
-    if (output == SAG_RENDER_DEPTH) SAG_AUX_LAUNCH((k_render_aux_list<R_OUT_DEPTH>), d_ids);
-    else SAG_AUX_LAUNCH((k_render_aux_list<R_OUT_SEG>), d_ids);
-  } else {
-    if (output == SAG_RENDER_DEPTH) SAG_AUX_LAUNCH((k_render_aux_rows<R_OUT_DEPTH>), d_mask);
-    else SAG_AUX_LAUNCH((k_render_aux_rows<R_OUT_SEG>), d_mask);
-  }
-#undef SAG_AUX_LAUNCH
-}
-int sag_render_aux_device(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags,
-                          const float* d_obs, const uint8_t* d_cost, const uint8_t* d_mask, void* d_out) {
-  if (!c || !d_out) return c ? fail(c, SAG_ERR_ARG, "sag_render_aux_device: null argument") : SAG_ERR_ARG;
-  if (int rc = aux_args_ok(c, "sag_render_aux_device", output, camera, width, height)) return rc;
-  if (reinterpret_cast<uintptr_t>(d_out) % aux_pixel_bytes(output))
-    return fail(c, SAG_ERR_ARG, "sag_render_aux_device: d_out is not aligned to %d bytes", (int)aux_pixel_bytes(output));
-  HIPCHK(c, hipSetDevice(c->cfg.device));
-  aux_launch(c, output, camera, width, height, flags, d_obs, d_cost, d_mask, nullptr, c->N, d_out);
-  HIPCHK(c, hipGetLastError());
-  return SAG_OK;
-}
-// host buffer: the staging (d_rgb, grown through ensure_rgb so that rgb_bytes stays true for the next RGB call) holds the
-// index list, rounded up to 16 bytes, in front of the rows asked for; no list for env_ids == NULL (every env, masked form)
-int sag_render_aux(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags, const int32_t* env_ids,
-                   int32_t n, void* out) {
-  if (!c) return SAG_ERR_ARG;
-  if (int rc = aux_args_ok(c, "sag_render_aux", output, camera, width, height)) return rc;
-  if (!env_ids) n = c->N;
-  if (n < 0 || (n > 0 && !out)) return fail(c, SAG_ERR_ARG, "sag_render_aux: n %d or a null argument", n);
+  if (int rc = render_args_ok(c, who, output, camera, width, height)) return rc;   // (before the sizes below are taken from it)
+  if (n < 0 || (n > 0 && !out)) return fail(c, SAG_ERR_ARG, "%s: n %d or a null argument", who, n);
   for (int32_t j = 0; env_ids && j < n; j++)
-    if (env_ids[j] < 0 || env_ids[j] >= c->N) return fail(c, SAG_ERR_ARG, "sag_render_aux: env %d (entry %d) of %d envs", env_ids[j], j, c->N);
+    if (env_ids[j] < 0 || env_ids[j] >= c->N) return fail(c, SAG_ERR_ARG, "%s: env %d (entry %d) of %d envs", who, env_ids[j], j, c->N);
   if (n == 0) return SAG_OK;
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const size_t list = env_ids ? ((size_t)n * sizeof(int32_t) + 15) & ~(size_t)15 : 0;
-  const size_t bytes = (size_t)n * width * height * aux_pixel_bytes(output);
+  const size_t bytes = (size_t)n * width * height * render_pixel_bytes(output);
   if (int rc = ensure_rgb(c, list + bytes)) return rc;
   // (the stream is joined below: env_ids has been read when the call returns)
   if (env_ids) HIPCHK(c, hipMemcpyAsync(c->d_rgb, env_ids, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-  aux_launch(c, output, camera, width, height, flags, (const float*)c->d_obs, (const uint8_t*)c->d_cost, nullptr,
-             env_ids ? reinterpret_cast<const int32_t*>(c->d_rgb) : nullptr, n, c->d_rgb + list);
-  HIPCHK(c, hipGetLastError());
+  if (int rc = render_launch(c, who, output, camera, width, height, flags, (const float*)c->d_obs, (const uint8_t*)c->d_cost, nullptr,
+                             env_ids ? reinterpret_cast<const int32_t*>(c->d_rgb) : nullptr, n, c->d_rgb + list)) return rc;
   HIPCHK(c, hipMemcpyAsync(out, c->d_rgb + list, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return SAG_OK;
+}
+
+int sag_render_device(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
+                      const uint8_t* d_cost, void* d_out) {
+  return sag_render_rows_device(c, camera, width, height, flags, d_obs, d_cost, nullptr, d_out);
+}
+// the envs of a device mask, each into its own row: the grid is sized for n_envs whatever the mask holds, and a workgroup
+// whose byte is zero returns at once (k_render_rows) - nothing the host decides, so it follows a reset on the stream.
+// A NULL mask launches k_render_rgb.
+int sag_render_rows_device(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const float* d_obs,
+                           const uint8_t* d_cost, const uint8_t* d_mask, void* d_out) {
+  return render_launch(c, d_mask ? "sag_render_rows_device" : "sag_render_device", R_OUT_RGB, camera, width, height, flags, d_obs, d_cost,
+                       d_mask, nullptr, c ? c->N : 0, d_out);
+}
+int sag_render(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, uint8_t* out) {
+  return render_to_host(c, "sag_render", R_OUT_RGB, camera, width, height, flags, nullptr, c ? c->N : 0, out);
+}
+int sag_render_envs(sag_ctx* c, int32_t camera, int32_t width, int32_t height, int32_t flags, const int32_t* env_ids, int32_t n,
+                    uint8_t* out) {
+  if (c && !env_ids)   // (no list is not "every env" here: it goes with n == 0 alone)
+    return n ? fail(c, SAG_ERR_ARG, "sag_render_envs: n %d or a null argument", n) : render_args_ok(c, "sag_render_envs", R_OUT_RGB, camera, width, height);
+  return render_to_host(c, "sag_render_envs", R_OUT_RGB, camera, width, height, flags, env_ids, n, out);
+}
+// depth / segmentation: output 0, the colour image, has the entry points above
+int sag_render_aux_device(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags,
+                          const float* d_obs, const uint8_t* d_cost, const uint8_t* d_mask, void* d_out) {
+  if (c && output == R_OUT_RGB) return fail(c, SAG_ERR_ARG, "sag_render_aux_device: unknown output 0");
+  return render_launch(c, "sag_render_aux_device", output, camera, width, height, flags, d_obs, d_cost, d_mask,
+                       nullptr, c ? c->N : 0, d_out);
+}
+// env_ids == NULL: every env, n is ignored
+int sag_render_aux(sag_ctx* c, int32_t output, int32_t camera, int32_t width, int32_t height, int32_t flags, const int32_t* env_ids,
+                   int32_t n, void* out) {
+  if (c && output == R_OUT_RGB) return fail(c, SAG_ERR_ARG, "sag_render_aux: unknown output 0");
+  return render_to_host(c, "sag_render_aux", output, camera, width, height, flags, env_ids, c && !env_ids ? c->N : n, out);
 }
 // rgb_observation: the 64 x 64 image of the robot's own camera, no overlays
 int sag_render_rgb_device(sag_ctx* c, void* d_out) { return sag_render_device(c, SAG_CAM_VISION, R_W, R_H, 0, nullptr, nullptr, d_out); }

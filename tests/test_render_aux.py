@@ -1,5 +1,5 @@
 """Depth and segmentation images of the device ray caster (sag_render_aux, sag_render_aux_device; csrc/sag_render.hpp
-k_render_aux_rows / k_render_aux_list) against the NumPy statement tests/render_aux_ref.py, which takes its geoms, camera
+k_render_rows<OUT> / k_render_list<OUT> with r_trace_nearest) against the NumPy statement tests/render_aux_ref.py, which takes its geoms, camera
 and rays from render_ref.  The acceptance rule is render_aux_ref.check_seg / check_depth: at decided, untied pixels class and
 instance equal and depth within one float32 step; at tied pixels either tied geom; at undecided pixels one of the five
 samples; at most render_ref.UNDECIDED_CAP of a case's pixels undecided.  The cases are ten of test_render_ref.CASES."""

@@ -1,5 +1,5 @@
-"""The ray caster k_render_rgb (csrc/sag_render.hpp) and the oracle's twin of it (oracle/sag_oracle_render.inc) against the
-independent per-pixel reference tests/render_ref.py.  One list of cases, used three times:
+"""The ray caster k_render_rgb (csrc/sag_render.hpp: r_render_env<R_OUT_RGB>, the colour branch of its pixel loop) and the oracle's twin
+of it (oracle/sag_oracle_render.inc) against the independent per-pixel reference tests/render_ref.py.  One list of cases, used three times:
   (a) reference vs oracle, no GPU: judges the oracle;
   (b) device vs reference through the C ABI (sag_render_device into a caller's buffer at a byte offset of 3);
   (c) the cases of (b) on the ASan / UBSan host build of the library's sources.

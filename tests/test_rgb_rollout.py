@@ -1,6 +1,7 @@
-"""Rendering a chosen subset of the envs (k_render_rows / k_render_list of csrc/sag_render.hpp, sag_render_rows_device and
-sag_render_envs) and what the env builds on it: rgb_observation inside the stream-ordered episode loop
-(time_limit, auto_reset, reset(mask, sync=False)), the masked render of the synchronous reset(mask), and render(envs=...).
+"""Rendering a chosen subset of the envs (k_render_rows<OUT> / k_render_list<OUT> of csrc/sag_render.hpp through the host's
+render_launch / render_to_host: sag_render_rows_device and sag_render_envs) and what the env builds on it: rgb_observation
+inside the stream-ordered episode loop (time_limit, auto_reset, reset(mask, sync=False)), the masked render of the synchronous
+reset(mask), and render(envs=...).
 
 Every comparison is byte-exact against the whole-batch render of the same state, which tests/test_render_ref.py ties to the
 independent per-pixel reference.  Every GPU test here also runs on the host build of the device sources (tests/hostemu) at
@@ -95,6 +96,76 @@ def test_masked_render_writes_the_rows_of_its_mask_only(nat, case):
     for p in (d_obs, d_cost, img):
       c.dev_free(p)
     dm.free(); c.close()
+
+
+@pytest.mark.gpu
+def test_rgb_entry_points_refuse_bad_arguments_and_agree(nat):
+  """The C level of the four colour entry points on the 3-env scene of test_render_aux._three (7 x 5, overlays).  A bad
+  camera, a bad size, a NULL out or a listed index outside [0, n_envs) returns SAG_ERR_ARG and leaves a sentinel-filled buffer
+  as it was; sag_render_envs with n == 0 returns SAG_OK and writes nothing, with and without null pointers.  Then
+  sag_render_device, sag_render_rows_device with a NULL and with an all-ones mask, sag_render and sag_render_envs([0, 1, 2])
+  give byte-equal rows."""
+  import ctypes as C
+  from test_render_aux import ERR_ARG, SENTINEL, _Overlay, _three
+  ctx, cam, W, H, obs, cost = _three(nat)   # (the step of _context left obs / cost in the context's own buffers: the host forms' overlays)
+  lib, h, n, size = ctx.lib, ctx.h, ctx.n_envs, ctx.n_envs * H * W * 3
+  assert n == 3
+  ov = _Overlay(ctx, True, obs, cost)
+  d_out, d_ones = ctx.dev_alloc(size), ctx.dev_alloc(n)
+  ctx.dev_upload(d_ones, np.ones(n, np.uint8))
+  u8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))     # noqa: E731
+  i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))    # noqa: E731
+
+  def host(ids, cam=cam, W=W, H=H, n_=None, null_out=False, null_ids=False):
+    """sag_render (ids None) or sag_render_envs into a host buffer of sentinel bytes sized for the good image"""
+    out = np.full(size, SENTINEL, np.uint8)
+    o = None if null_out else u8(out)
+    if ids is None:
+      return lib.sag_render(h, cam, W, H, 1, o), out
+    ids = np.array(ids, np.int32)
+    return lib.sag_render_envs(h, cam, W, H, 1, None if null_ids else i32(ids), len(ids) if n_ is None else n_, o), out
+
+  def device(mask, cam=cam, W=W, H=H, null_out=False):
+    """sag_render_device (mask 'none') or sag_render_rows_device (mask None: NULL) into a device buffer of sentinel bytes"""
+    ctx.dev_upload(d_out, np.full(size, SENTINEL, np.uint8))
+    o = None if null_out else d_out
+    if mask == 'none':
+      rc = lib.sag_render_device(h, cam, W, H, 1, ov.d_obs, ov.d_cost, o)
+    else:
+      rc = lib.sag_render_rows_device(h, cam, W, H, 1, ov.d_obs, ov.d_cost, mask, o)
+    ctx.wait()
+    return rc, ctx.dev_download(d_out, (size,), np.uint8)
+
+  bad = (('camera 4', dict(cam=4)), ('camera -1', dict(cam=-1)), ('width 0', dict(W=0)), ('height 4097', dict(H=4097)),
+         ('NULL out', dict(null_out=True)))
+  for what, kw in bad:
+    for name, call in (('sag_render', lambda: host(None, **kw)), ('sag_render_envs', lambda: host([0, 1, 2], **kw)),
+                       ('sag_render_device', lambda: device('none', **kw)), ('sag_render_rows_device', lambda: device(d_ones, **kw)),
+                       ('sag_render_rows_device, NULL mask', lambda: device(None, **kw))):
+      rc, buf = call()
+      assert rc == ERR_ARG, f'{name}, {what}: {rc}'
+      assert (buf == SENTINEL).all(), f'{name}, {what}: the buffer was written'
+  for what, kw in (('an index of n_envs', dict(ids=[0, n])), ('an index of -1', dict(ids=[-1, 0])), ('n < 0', dict(ids=[0, 1], n_=-1)),
+                   ('a NULL list', dict(ids=[0, 1], null_ids=True))):
+    rc, buf = host(**kw)
+    assert rc == ERR_ARG, f'sag_render_envs, {what}: {rc}'
+    assert (buf == SENTINEL).all(), f'sag_render_envs, {what}: the buffer was written'
+  # an empty list is not an error, whatever the pointers
+  rc, buf = host([1], n_=0)
+  assert rc == 0 and (buf == SENTINEL).all(), 'n == 0 wrote something'
+  assert host([1], n_=0, null_out=True)[0] == 0 and host([1], n_=0, null_out=True, null_ids=True)[0] == 0
+  # the five ways to the whole batch
+  rc, whole = device('none')
+  assert rc == 0 and not (whole.reshape(n, -1) == SENTINEL).all(1).any()
+  for name, got in (('sag_render_rows_device, NULL mask', device(None)), ('sag_render_rows_device, all ones', device(d_ones)),
+                    ('sag_render', host(None)), ('sag_render_envs', host([0, 1, 2]))):
+    assert got[0] == 0, name
+    np.testing.assert_array_equal(got[1], whole, err_msg=name)
+  np.testing.assert_array_equal(whole.reshape(n, H, W, 3), ctx.render(cam, W, H, overlays=True))
+  for p in (d_out, d_ones):
+    ctx.dev_free(p)
+  ov.free()
+  ctx.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1,18 +1,20 @@
-"""Time of the depth and segmentation renders beside the colour render (profiles/render_aux.txt is such a table).
+"""Time of the renders of this build beside the parent's (profiles/render_aux.txt, profiles/render_unify_time.txt are such
+tables).
 
   python tools/render_aux_time.py [out.txt] --parent-tree DIR --parent2 LIB [--rounds 5]
 
 4096 doggo / haul_box and 4096 point / go_to_goal envs, 64 x 64, the robot's `vision` camera, no overlays.  Every measurement
 is a process of its own, one at a time; the first that fails ends the run.  Wall time over a window of 20 back-to-back
-launches after warm-up, one sag_wait at the end of the window.  Per round, interleaved:
-  parent   sag_render_rgb_device of --parent-tree (a checkout of the parent commit with its library built; its own package
-           loads it)
-  this     sag_render_rgb_device of this build
-  parent2  the same of --parent2 (the library of a second build of the parent, loaded by the parent's package):
-           |parent2 - parent| per round is the spread of the measurement (A/A)
-  depth, segmentation   sag_render_aux_device of this build
+launches after warm-up, one sag_wait at the end of the window.  Four figures: rgb (sag_render_rgb_device), depth and
+segmentation (sag_render_aux_device), masked (sag_render_rows_device, every second byte of the mask set).  Per round and
+figure, interleaved:
+  parent   --parent-tree (a checkout of the parent commit with its library built; its own package loads it)
+  this     this build
+  parent2  --parent2 (the library of a second build of the parent, loaded by the parent's package):
+           |parent2 - parent| is the spread of the measurement (A/A)
 Two conditions, printed with the figures; the exit status is 1 when one does not hold:
-  (1) this build's RGB median exceeds the parent's by no more than the largest |parent2 - parent| of the run;
+  (1) for each figure, this build's median exceeds the parent's by no more than the largest |parent2 - parent| of the run
+      (any round, any figure of the robot config);
   (2) the median of each auxiliary output does not exceed this build's RGB median."""
 import json
 import os
@@ -37,7 +39,11 @@ def child(what, robot, task, n):
   c.dev_fill_actions(b['act'], 0)
   for _ in range(10):   # (the Doggos land)
     c.step_device(b['act'], None, -1, b['obs'], b['rew'], b['cost'], b['done'], b['met'])
-  fn = (lambda: c.render_rgb_device(b['img'])) if what == 'rgb' else (lambda: c.render_aux_device(what, b['img']))
+  if what == 'masked':
+    b['mask'] = c.dev_alloc(n)
+    c.dev_upload(b['mask'], (np.arange(n) % 2).astype(np.uint8))
+  fn = {'rgb': lambda: c.render_rgb_device(b['img']), 'masked': lambda: c.render_rows_device(b['mask'], b['img'])}.get(
+      what, lambda: c.render_aux_device(what, b['img']))
   for _ in range(3):
     fn()
   c.wait()
@@ -79,27 +85,30 @@ def main():
         f.write('\n'.join(lines) + '\n')
 
   med = lambda v: sorted(v)[len(v) // 2]   # noqa: E731
-  cols = ['parent', 'this', 'parent2', 'depth', 'segmentation']
+  figs, builds = ['rgb', 'depth', 'segmentation', 'masked'], ['parent', 'this', 'parent2']
   ok = True
   say(f'64 x 64 vision renders, ms per launch (window of {REPS}), {rounds} interleaved rounds, a process per figure')
   for robot, task, n in (('doggo', 'haul_box', 4096), ('point', 'go_to_goal', 4096)):
-    rows = []
+    rows = {f: [] for f in figs}
     for k in range(rounds):
-      r = [run(parent, None, 'rgb', robot, task, n), run(None, None, 'rgb', robot, task, n), run(parent, parent2, 'rgb', robot, task, n),
-           run(None, None, 'depth', robot, task, n), run(None, None, 'segmentation', robot, task, n)]
-      rows.append(r)
-      say(f'   {robot}/{task} {n}  round {k}: ' + '  '.join(f'{c} {v:8.4f}' for c, v in zip(cols, r)))
-    m = {c: med([r[j] for r in rows]) for j, c in enumerate(cols)}
-    aa = max(abs(r[2] - r[0]) for r in rows)
-    say(f'   {robot}/{task} {n}  medians: ' + '  '.join(f'{c} {m[c]:.4f}' for c in cols))
-    c1 = m['this'] - m['parent'] <= aa
-    say(f'   {robot}/{task} {n}  (1) this - parent {1e3 * (m["this"] - m["parent"]):+.1f} us against the largest A/A difference '
-        f'|parent2 - parent| {1e3 * aa:.1f} us: {"holds" if c1 else "DOES NOT HOLD"}')
-    for c in ('depth', 'segmentation'):
-      c2 = m[c] <= m['this']
-      say(f'   {robot}/{task} {n}  (2) {c} {m[c]:.4f} against RGB {m["this"]:.4f} ({m[c] / m["this"]:.2f} x): {"holds" if c2 else "DOES NOT HOLD"}')
+      for f in figs:
+        r = [run(parent, None, f, robot, task, n), run(None, None, f, robot, task, n), run(parent, parent2, f, robot, task, n)]
+        rows[f].append(r)
+        say(f'   {robot}/{task} {n}  round {k} {f:12s}: ' + '  '.join(f'{c} {v:8.4f}' for c, v in zip(builds, r)))
+    m = {f: {c: med([r[j] for r in rows[f]]) for j, c in enumerate(builds)} for f in figs}
+    aa = max(abs(r[2] - r[0]) for f in figs for r in rows[f])
+    for f in figs:
+      say(f'   {robot}/{task} {n}  medians {f:12s}: ' + '  '.join(f'{c} {m[f][c]:.4f}' for c in builds))
+    for f in figs:
+      c1 = m[f]['this'] - m[f]['parent'] <= aa
+      say(f'   {robot}/{task} {n}  (1) {f}: this - parent {1e3 * (m[f]["this"] - m[f]["parent"]):+.1f} us against the largest A/A difference '
+          f'|parent2 - parent| {1e3 * aa:.1f} us: {"holds" if c1 else "DOES NOT HOLD"}')
+      ok = ok and c1
+    for f in ('depth', 'segmentation'):
+      c2 = m[f]['this'] <= m['rgb']['this']
+      say(f'   {robot}/{task} {n}  (2) {f} {m[f]["this"]:.4f} against RGB {m["rgb"]["this"]:.4f} ({m[f]["this"] / m["rgb"]["this"]:.2f} x): '
+          f'{"holds" if c2 else "DOES NOT HOLD"}')
       ok = ok and c2
-    ok = ok and c1
   sys.exit(0 if ok else 1)
 
 
