@@ -497,6 +497,53 @@ enum sag_fork_flags { SAG_FORK_SAME_STREAM = 1 };
 int sag_fork_device(sag_ctx* dst, sag_ctx* src, const int32_t* d_src, int32_t flags);
 /* Envs copied / envs rejected by sag_fork_device into ctx since the last call with clear != 0.  Synchronises the stream. */
 int sag_fork_counts(sag_ctx* ctx, int32_t clear, uint64_t* n_copied, uint64_t* n_rejected);
+/* ctx's stream waits for everything enqueued so far on producer's (a context on the same device): what ctx enqueues next may
+ * read what producer's stream writes - a planner's action buffer read by the env's step.  No host wait.  producer == ctx: SAG_OK,
+ * nothing to do.  SAG_ERR_ARG: NULL, another device. */
+int sag_wait_for(sag_ctx* ctx, sag_ctx* producer);
+
+/* ---- shooting planner on the device (throughput mode) -------------------------------------------
+ * The other half of a planner built on sag_fork_device: a context of n_envs = G * K envs holds K candidates for each of G real
+ * envs (groups are consecutive: candidate k of group g is env g * K + k), and one planning iteration is
+ *   sag_fork_device(plan ctx, real ctx, d_src = i / K)   every real env broadcast to its K candidates
+ *   sag_plan_sample_device                               K action sequences per group from mean / sigma
+ *   sag_plan_score_device                                H steps without observations; return and cost per candidate
+ *   sag_plan_refit_device                                rank under the cost budget, refit mean / sigma to the elites
+ * all enqueued on the context stream: no host wait, no host copy.  Every buffer is fp32 on the context's device, h-major:
+ *   plans [H][n_envs][nu]    mean, sigma [H][G][nu]    (8-byte aligned; step t's actions and the mean's first action are contiguous)
+ *   score [n_envs][4] = {discounted return, discounted cost, steps alive, goals met}, 16-byte aligned
+ * Refused with SAG_ERR_ARG and nothing enqueued: a NULL or misaligned pointer, K < 1, n_envs % K != 0, H < 1, E < 1, E > K, gamma
+ * outside (0, 1] or non-finite, a negative or non-finite sigma_min / sigma_init; SAG_ERR_STATE: a context without a layout.
+ *
+ * sag_plan_sample_device: plans[h][g*K+k][u] = clamp(mean[h][g][u] + sigma[h][g][u] * z, -1, 1), z = 0 for k = 0 (the current
+ * mean is always a candidate).  z is a standard normal of the counter-based generator under the context key (sag_set_seed) on
+ * stream 4: with e = h * nu + u, the Philox4x32-10 block of the counter
+ *   word 0 = env_id0 (sag_set_tasks; 0 without tasks) + g*K + k    word 1 = draw    word 2 = e / 4    word 3 = 0x10000000
+ * gives e % 4 = 0, 1 the two normals (cos, sin) of the Box-Muller transform of its words 0, 1 and e % 4 = 2, 3 those of its
+ * words 2, 3 (the transform of the action noise: u = ((w >> 8) + 0.5) / 2^24 in fp32).  Word 3 is stream 4 placed above the 26 bits
+ * (episode nonce << 2 | stream) of streams 0 - 3.  The caller advances `draw` from call to call. */
+int sag_plan_sample_device(sag_ctx* ctx, int32_t K, int32_t H, const float* d_mean, const float* d_sigma, uint32_t draw,
+                           float* d_plans);
+/* Zeroes d_score, then H times: the step on actions d_plans + t * n_envs * nu (the device's own action noise and in-step draws,
+ * the robot's substeps, no observation), then per env still alive ret += w_t * reward, cost += w_t * (cost != 0), steps += 1,
+ * goals += goal_met != 0, with w_0 = 1, w_{t+1} = w_t * gamma in fp32 and the product and the sum rounded separately.  An env
+ * stops being alive after a step that reports done; that step is counted.  The context's state advances by H steps: fork again
+ * before the next scoring.  Pending external contacts are dropped, as by any step. */
+int sag_plan_score_device(sag_ctx* ctx, const float* d_plans, int32_t H, float gamma, float* d_score);
+/* Per group: the K candidates in a total order - feasible ones (score cost <= d_budget[g]; every one when d_budget is NULL)
+ * first, by higher return; then the infeasible ones by lower cost, then higher return; ties by lower k; a candidate whose return
+ * or cost is not finite after every finite one, by k.  The first E are the elites: mean[h][g][u] = (the sum of their plan
+ * values in ascending k, in fp32) * (1 / E), sigma = max(sigma_min, sqrt(mean squared deviation from that mean)).
+ * d_best[g] = the k of the first candidate, d_best_score[g] (or NULL) its score row.  d_budget: [G] floats or NULL. */
+int sag_plan_refit_device(sag_ctx* ctx, int32_t K, int32_t H, int32_t E, const float* d_plans, const float* d_score,
+                          const float* d_budget, float sigma_min, float* d_mean, float* d_sigma, int32_t* d_best,
+                          float* d_best_score);
+/* Receding-horizon warm start after the first action was taken: mean[h] = mean[h + 1], the last row 0, every sigma = sigma_init. */
+int sag_plan_shift_device(sag_ctx* ctx, int32_t G, int32_t H, float* d_mean, float* d_sigma, float sigma_init);
+/* mean = 0 and sigma = sigma_init for the groups with a non-zero byte of d_mask ([G] device bytes; NULL: every group): the
+ * episodes of these envs restarted. */
+int sag_plan_clear_device(sag_ctx* ctx, int32_t G, int32_t H, const uint8_t* d_mask, float* d_mean, float* d_sigma,
+                          float sigma_init);
 
 #ifdef __cplusplus
 }

@@ -7,6 +7,13 @@ the device, throughput mode only, and accepts a mask of envs to reset: envs.Batc
 from typing import Dict, Optional
 
 
+def __getattr__(name):
+  if name == 'ShootingPlanner':   # sag.ShootingPlanner(env, ...): a constrained CEM planner on the device (planner.py)
+    from safe_adaptation_gym_amd.planner import ShootingPlanner
+    return ShootingPlanner
+  raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
+
+
 def make(robot_name: str,
          task_name: Optional[str] = None,
          seed: int = 666,

@@ -35,7 +35,8 @@ EXPORTS = [
     'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_render_rows_device', 'sag_render_envs', 'sag_render_aux', 'sag_render_aux_device', 'sag_debug_doggo_coop',
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
-    'sag_episode_clear', 'sag_fork_device', 'sag_fork_counts'
+    'sag_episode_clear', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
+    'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device'
 ]
 
 
@@ -120,6 +121,12 @@ def load():
   lib.sag_episode_clear.argtypes = [vp, vp]
   lib.sag_fork_device.argtypes = [vp, vp, vp, C.c_int32]
   lib.sag_fork_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+  lib.sag_wait_for.argtypes = [vp, vp]
+  lib.sag_plan_sample_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_uint32, vp]
+  lib.sag_plan_score_device.argtypes = [vp, vp, C.c_int32, C.c_float, vp]
+  lib.sag_plan_refit_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, vp, vp, vp, vp]
+  lib.sag_plan_shift_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_float]
+  lib.sag_plan_clear_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_float]
   _lib = lib
   return lib
 
@@ -481,6 +488,37 @@ class Context:
     a, b = C.c_uint64(), C.c_uint64()
     self._check(self.lib.sag_fork_counts(self.h, int(bool(clear)), C.byref(a), C.byref(b)), 'sag_fork_counts')
     return a.value, b.value
+
+  def wait_for(self, producer):
+    """sag_wait_for: this context's stream waits for what is enqueued on `producer`'s (a Context on the same device); no
+    host wait."""
+    self._check(self.lib.sag_wait_for(self.h, producer.h), 'sag_wait_for')
+
+  # -- shooting planner (include/sag.h; planner.ShootingPlanner drives these) -------
+  def plan_sample(self, K, H, d_mean, d_sigma, draw, d_plans):
+    """sag_plan_sample_device: plans [H][n_envs][nu] = clamp(mean + sigma * z), candidate 0 of each group of K the mean."""
+    self._check(self.lib.sag_plan_sample_device(self.h, int(K), int(H), d_mean, d_sigma, int(draw) & 0xffffffff, d_plans),
+                'sag_plan_sample_device')
+
+  def plan_score(self, d_plans, H, gamma, d_score):
+    """sag_plan_score_device: H steps of this context on the plans, without observations; score [n_envs][4] = discounted
+    return, discounted cost, steps alive, goals met.  The context's state advances by H steps."""
+    self._check(self.lib.sag_plan_score_device(self.h, d_plans, int(H), float(gamma), d_score), 'sag_plan_score_device')
+
+  def plan_refit(self, K, H, E, d_plans, d_score, d_budget, sigma_min, d_mean, d_sigma, d_best, d_best_score=None):
+    """sag_plan_refit_device: rank each group's K candidates under d_budget ([G] floats or None), refit mean / sigma to the
+    E elites, d_best [G] int32 = the first candidate."""
+    self._check(self.lib.sag_plan_refit_device(self.h, int(K), int(H), int(E), d_plans, d_score, d_budget, float(sigma_min), d_mean,
+                                               d_sigma, d_best, d_best_score), 'sag_plan_refit_device')
+
+  def plan_shift(self, G, H, d_mean, d_sigma, sigma_init):
+    """sag_plan_shift_device: mean[h] = mean[h + 1], last row 0, sigma = sigma_init."""
+    self._check(self.lib.sag_plan_shift_device(self.h, int(G), int(H), d_mean, d_sigma, float(sigma_init)), 'sag_plan_shift_device')
+
+  def plan_clear(self, G, H, d_mask, d_mean, d_sigma, sigma_init):
+    """sag_plan_clear_device: mean = 0, sigma = sigma_init for the groups of d_mask ([G] bytes; None: all)."""
+    self._check(self.lib.sag_plan_clear_device(self.h, int(G), int(H), d_mask, d_mean, d_sigma, float(sigma_init)),
+                'sag_plan_clear_device')
 
   def set_seed(self, seed):
     """Key of the device-side generator of throughput mode (env.seed())."""

@@ -22,6 +22,7 @@
 #include "sag_reset.hpp"
 #include "sag_rollout.hpp"
 #include "sag_fork.hpp"
+#include "sag_plan.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -110,6 +111,9 @@ struct sag_ctx {
   std::vector<sag_task_desc> h_descs;
   unsigned long long* d_ftot = nullptr;
   hipEvent_t ev_xsrc = nullptr, ev_xdone = nullptr;
+  // sag_plan_*: alive flags of a scoring rollout and the ranks of a refit ([N] each), the second buffer of sag_plan_shift_device
+  uint8_t* d_palive = nullptr; int32_t* d_prank = nullptr;
+  float* d_pshift = nullptr; size_t pshift_floats = 0;
   std::string err;
 };
 
@@ -569,7 +573,7 @@ int sag_destroy(sag_ctx* c) {
   for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   void* bufs[] = {c->S, c->I, c->G, c->d_rows, c->d_count, c->d_kind, c->L_f, c->L_i, c->st_f, c->st_i, c->st_ids, c->d_act, c->d_noise,
                   c->d_tape, c->d_obs, c->d_rew, c->d_cost, c->d_done, c->d_met, c->d_used, c->scratch, c->d_rgb, c->d_dr, c->d_dg_sched, c->d_hot,
-                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot};
+                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot, c->d_palive, c->d_prank, c->d_pshift};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
@@ -997,6 +1001,138 @@ int sag_fork_counts(sag_ctx* c, int32_t clear, uint64_t* n_copied, uint64_t* n_r
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n_copied) *n_copied = tot[0];
   if (n_rejected) *n_rejected = tot[1];
+  return SAG_OK;
+}
+
+int sag_wait_for(sag_ctx* c, sag_ctx* producer) {
+  if (!c) return SAG_ERR_ARG;
+  if (!producer) return fail(c, SAG_ERR_ARG, "sag_wait_for: the producer context is NULL");
+  if (producer->cfg.device != c->cfg.device) return fail(c, SAG_ERR_ARG, "sag_wait_for: device %d and device %d", producer->cfg.device, c->cfg.device);
+  if (producer == c) return SAG_OK;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  HIPCHK(c, hipEventRecord(producer->ev_xdone, producer->stream));
+  HIPCHK(c, hipStreamWaitEvent(c->stream, producer->ev_xdone, 0));
+  return SAG_OK;
+}
+
+// ---- shooting planner (sag_plan.hpp) ----
+namespace {
+
+bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+bool plan_scale_ok(float x) { return std::isfinite(x) && x >= 0.0f; }
+
+// K candidates per group of a context: 0 if the arguments are refused (the message is set)
+int plan_groups(sag_ctx* c, const char* who, int32_t K, int32_t H) {
+  if (K < 1 || c->N % K != 0) { fail(c, SAG_ERR_ARG, "%s: K = %d does not divide the context's %d envs", who, K, c->N); return 0; }
+  if (H < 1) { fail(c, SAG_ERR_ARG, "%s: H = %d", who, H); return 0; }
+  return c->N / K;
+}
+
+int ensure_plan_scratch(sag_ctx* c) {
+  if (c->d_palive) return 0;
+  HIPCHK(c, hipMalloc(&c->d_prank, (size_t)c->N * sizeof(int32_t)));
+  HIPCHK(c, hipMalloc(&c->d_palive, (size_t)c->N));
+  return 0;
+}
+
+}  // namespace
+
+int sag_plan_sample_device(sag_ctx* c, int32_t K, int32_t H, const float* d_mean, const float* d_sigma, uint32_t draw, float* d_plans) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d_mean || !d_sigma || !d_plans || misaligned(d_mean, 8) || misaligned(d_sigma, 8) || misaligned(d_plans, 8))
+    return fail(c, SAG_ERR_ARG, "sag_plan_sample_device: NULL buffer, or one that is not 8-byte aligned");
+  if (!plan_groups(c, "sag_plan_sample_device", K, H)) return SAG_ERR_ARG;
+  if (!c->have_layout) return fail(c, SAG_ERR_STATE, "sag_plan_sample_device before sag_set_layout");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t lanes = (size_t)((H * c->rb.nu + 3) / 4) * (size_t)c->N;
+  hipLaunchKernelGGL(k_plan_sample, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, c->stream, c->N, K, H, c->rb.nu, (uint32_t)c->env_id0, draw,
+                     (uint32_t)(c->cfg.seed & 0xffffffffu), (uint32_t)(c->cfg.seed >> 32), d_mean, d_sigma, d_plans);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+// H times: the step on step t's block of the plans - no observation, context-owned reward / cost / done / met - then the accumulation
+int sag_plan_score_device(sag_ctx* c, const float* d_plans, int32_t H, float gamma, float* d_score) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d_plans || !d_score || misaligned(d_plans, 8) || misaligned(d_score, 16))
+    return fail(c, SAG_ERR_ARG, "sag_plan_score_device: NULL buffer, d_plans not 8-byte or d_score not 16-byte aligned");
+  if (H < 1) return fail(c, SAG_ERR_ARG, "sag_plan_score_device: H = %d", H);
+  if (!(gamma > 0.0f && gamma <= 1.0f)) return fail(c, SAG_ERR_ARG, "sag_plan_score_device: gamma = %g is outside (0, 1]", (double)gamma);
+  if (!c->have_layout) return fail(c, SAG_ERR_STATE, "sag_plan_score_device before sag_set_layout");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  int rc = ensure_plan_scratch(c);
+  if (rc) return rc;
+  const size_t N = (size_t)c->N;
+  HIPCHK(c, hipMemsetAsync(d_score, 0, N * 4 * sizeof(float), c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_palive, 1, N, c->stream));
+  float w = 1.0f;
+  for (int t = 0; t < H; t++) {
+    rc = launch_step(c, d_plans + (size_t)t * N * c->rb.nu, nullptr, nullptr, 0, -1, nullptr, c->d_rew, c->d_cost, c->d_done, c->d_met, nullptr, 0);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_plan_accumulate, dim3((c->N + 255) / 256), dim3(256), 0, c->stream, c->N, w, c->d_rew, c->d_cost, c->d_done, c->d_met,
+                       c->d_palive, reinterpret_cast<float4*>(d_score));
+    HIPCHK(c, hipGetLastError());
+    w = w * gamma;
+  }
+  return SAG_OK;
+}
+
+int sag_plan_refit_device(sag_ctx* c, int32_t K, int32_t H, int32_t E, const float* d_plans, const float* d_score, const float* d_budget,
+                          float sigma_min, float* d_mean, float* d_sigma, int32_t* d_best, float* d_best_score) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d_plans || !d_score || !d_mean || !d_sigma || !d_best || misaligned(d_plans, 8) || misaligned(d_score, 16) || misaligned(d_budget, 4) ||
+      misaligned(d_mean, 8) || misaligned(d_sigma, 8) || misaligned(d_best, 4) || misaligned(d_best_score, 16))
+    return fail(c, SAG_ERR_ARG, "sag_plan_refit_device: NULL or misaligned buffer (plans, mean, sigma 8 bytes; score, best_score 16; budget, best 4)");
+  const int G = plan_groups(c, "sag_plan_refit_device", K, H);
+  if (!G) return SAG_ERR_ARG;
+  if (E < 1 || E > K) return fail(c, SAG_ERR_ARG, "sag_plan_refit_device: E = %d elites of K = %d candidates", E, K);
+  if (!plan_scale_ok(sigma_min)) return fail(c, SAG_ERR_ARG, "sag_plan_refit_device: sigma_min = %g", (double)sigma_min);
+  if (!c->have_layout) return fail(c, SAG_ERR_STATE, "sag_plan_refit_device before sag_set_layout");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  int rc = ensure_plan_scratch(c);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_plan_refit, dim3(G), dim3(PLAN_REFIT_THREADS), 0, c->stream, c->N, K, H, c->rb.nu, E, d_plans,
+                     reinterpret_cast<const float4*>(d_score), d_budget, sigma_min, c->d_prank, d_mean, d_sigma, d_best,
+                     reinterpret_cast<float4*>(d_best_score));
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+static int plan_table_ok(sag_ctx* c, const char* who, int32_t G, int32_t H, const float* d_mean, const float* d_sigma, float sigma_init) {
+  if (!d_mean || !d_sigma || misaligned(d_mean, 8) || misaligned(d_sigma, 8))
+    return fail(c, SAG_ERR_ARG, "%s: NULL buffer, or one that is not 8-byte aligned", who);
+  if (G < 1 || H < 1) return fail(c, SAG_ERR_ARG, "%s: G = %d, H = %d", who, G, H);
+  if (!plan_scale_ok(sigma_init)) return fail(c, SAG_ERR_ARG, "%s: sigma_init = %g", who, (double)sigma_init);
+  if (!c->have_layout) return fail(c, SAG_ERR_STATE, "%s before sag_set_layout", who);
+  return 0;
+}
+
+int sag_plan_shift_device(sag_ctx* c, int32_t G, int32_t H, float* d_mean, float* d_sigma, float sigma_init) {
+  if (!c) return SAG_ERR_ARG;
+  int rc = plan_table_ok(c, "sag_plan_shift_device", G, H, d_mean, d_sigma, sigma_init);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t row = (size_t)G * c->rb.nu, total = (size_t)H * row;
+  if (c->pshift_floats < total) {   // (the first call for a table of this size; a buffer in use by the stream is not freed under it)
+    if (c->d_pshift) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_pshift); }
+    c->d_pshift = nullptr; c->pshift_floats = 0;
+    HIPCHK(c, hipMalloc(&c->d_pshift, total * sizeof(float)));
+    c->pshift_floats = total;
+  }
+  hipLaunchKernelGGL(k_plan_shift, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, H, (int)row, d_mean, c->d_pshift, d_sigma, sigma_init);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(d_mean, c->d_pshift, total * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+  return SAG_OK;
+}
+
+int sag_plan_clear_device(sag_ctx* c, int32_t G, int32_t H, const uint8_t* d_mask, float* d_mean, float* d_sigma, float sigma_init) {
+  if (!c) return SAG_ERR_ARG;
+  int rc = plan_table_ok(c, "sag_plan_clear_device", G, H, d_mean, d_sigma, sigma_init);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const size_t total = (size_t)H * G * c->rb.nu;
+  hipLaunchKernelGGL(k_plan_clear, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, H, G, c->rb.nu, d_mask, d_mean, d_sigma, sigma_init);
+  HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }
 
