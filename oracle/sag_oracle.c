@@ -1193,9 +1193,12 @@ static int world_forward(World* w, const OEnv* e, const real* ctrl, const Sol* s
     if (nc) w->act_v[k] = 1;
   }
   if (has_box) {
-    if (w->box_kind == SAG_BOX_BALL) {
+    if (w->box_kind == SAG_BOX_BALL && w->robot_id == SAG_ROBOT_POINT) {
       /* the ball's centre is .04 above the robot sphere's: they touch at horizontal distance
-       * sqrt(.24^2 - .04^2) - the ball presents radius .1366 to the sphere, .14 to the arrow */
+       * sqrt(.24^2 - .04^2) - the ball presents radius .1366 to the sphere, .14 to the arrow.
+       * (The Point only: the Car's eight geoms all meet the ball's full radius.  Until the directed contact tests this
+       * branch also took the Car, whose geoms 0 and 1 - chassis and back bumper - stood in for sphere and arrow
+       * and whose other six, the front bumper it dribbles with among them, passed through the ball.) */
       Body sphere = w->robot, arrow = w->robot;
       sphere.ngeom = 1; arrow.ngeom = 1; arrow.g[0] = w->robot.g[1];
       Body ball = w->box;

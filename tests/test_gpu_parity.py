@@ -14,7 +14,7 @@ from oracle_lib import Oracle
 pytestmark = pytest.mark.gpu
 
 OBS_TOL = 2e-5     # fp32 state -> fp64 lidar closeness, sensors
-STATE_TOL = 1e-4   # one-step qpos/qvel: HIP fp32 vs oracle fp64 from the same fp32 state
+STATE_TOL = bu.STATE_TOL   # 1e-4, one-step qpos/qvel: HIP fp32 vs oracle fp64 from the same fp32 state
 REW_TOL = 2e-6
 
 
@@ -253,7 +253,7 @@ def _lidar_e2e_bound(nat, d_rf, o_rf):
 
 
 CAR_TASKS = ['go_to_goal', 'push_box', 'press_buttons', 'unsupervised', 'catch_goal', 'haul_box']
-MIXED = 'multitask'  # per-env task ids drawn by the benchmark's TaskSampler (BASELINE config 4 shape)
+MIXED = bu.MIXED  # 'multitask': per-env task ids drawn by the benchmark's TaskSampler (BASELINE config 4 shape)
 
 
 @pytest.mark.parametrize('robot,task', [('point', t) for t in LOCKSTEP_TASKS] + [('car', t) for t in CAR_TASKS] +
@@ -401,25 +401,10 @@ def _lockstep(nat, oracle, oracle32, robot, task, scale, throughput=False, reset
     o_rf, o_ri = oracle.batch_records(arr)
     o32_rf, _ = oracle32.batch_records(arr32)
     # state: rows outside the tolerance are counted, not hidden
-    tol64 = np.full(d_rf.shape[1], STATE_TOL)
-    tol32 = np.full(d_rf.shape[1], 2e-5)
-    # rest capture (REST_W = 1e-4 rad/s) and contacts at zero depth between resting bodies are
-    # decided at float rounding: free-body spin rates may differ by that scale
-    for wf in [46] + [81 + 6 * k + 5 for k in range(10)]:
-      tol32[wf] = 2e-4
-      tol64[wf] = 2e-4
-    if robot == 'car':
-      # the rear ball (2.6 g, I = 2.6e-6 kg m^2, joint damping 1e-3: time constant I / d = 2.6 ms < h) and the wheels
-      # are stiff spinning parts: the fp32 oracle (world-frame friction, divisions) and the device (body-frame
-      # constants, reciprocals) round differently by an ulp per operation, amplified here ~100x; values are O(10) rad/s
-      for wf in range(144, 149):
-        tol32[wf] = 2e-4
-    if task in ('dribble_ball', MIXED):
-      # the ball's spin (unobservable; I = 4.5e-8 kg m^2) is set by friction torques of a stiff,
-      # underdamped contact (solref .018 .2): fp32 rounding is amplified ~1000x there
-      tol64[46] = tol32[46] = 5e-3
-    bad64 = (np.abs(d_rf - o_rf) > tol64 + tol64 * np.abs(o_rf)).any(1)
-    bad32 = (np.abs(d_rf - o32_rf) > tol32 + tol32 * np.abs(o32_rf)).any(1)
+    # (the per-column table is bu.lockstep_state_tol: shared with tests/test_contact_branches.py)
+    tol64, tol32 = bu.lockstep_state_tol(robot, task, d_rf.shape[1])
+    bad64 = bu.rows_outside(d_rf, o_rf, tol64)
+    bad32 = bu.rows_outside(d_rf, o32_rf, tol32)
     viol64 += int(bad64.sum())
     viol32 += int(bad32.sum())
     bad64_env += bad64; bad32_env += bad32

@@ -2,8 +2,10 @@
 mask of collide_list_nb, which evaluates the same four inequalities in the two body frames) must be CONSERVATIVE: a
 pair it rejects has no vertex of either box strictly inside the other, which is all bb_contact looks for.  This is a
 NumPy restatement of the inequalities in float32 (the kernels' precision, fused or not) against the vertex criterion
-in float64, on random and on near-touching configurations.  The device code itself is pinned by the bit-identical
-trajectory comparison against the plain pair loops (tests/diag_traj.py --cmp)."""
+in float64, on random and on near-touching configurations.  The device code itself is pinned by
+tests/test_contact_branches.py (dense directed states in which box pairs behind the cull overlap by the hundred - arrow /
+vase, vase / vase, the five-geom box, the Car's eight geoms - stepped against both builds of the oracle) and by the
+bit-identical trajectory comparison against the plain pair loops (tests/diag_traj.py --cmp)."""
 import numpy as np
 
 SAT_EPS = np.float32(1e-5)
