@@ -43,39 +43,59 @@ __host__ __device__ constexpr size_t iaddr(int w, size_t N, size_t i) {
 // plain field-major layout), and a GATHER - the busy kernel reading scattered envs - moves a quarter
 // of the cache lines per useful float.  The order inside the device record follows what the step
 // prologue reads together, not the order of the ABI record (k_install / k_extract translate):
-//   0 robot x y yaw vx | 4 vy w goal_x goal_y | 8 last0 gear damp action_noise | 12 ctrl_scale0,1
-//   vase_size pillar_size | 16 pillars | 20..37 hazards, 38 hazard_size, 39 bound |
-//   40.. positions (x y yaw) of the 11 free bodies | 76.. their velocities (vx vy w) |
-//   112 buttons | 124 catch | 128 last1,2 | 130 keepouts | 136 rebuild pose | 140 ctrl_scale2.. |
-//   152 robot extension
+//   0 robot x y yaw vx | 4 vy w last0 pillar_size | 8 goal_x goal_y gear damp | 12 action_noise
+//   ctrl_scale0,1 vase_size | 16 pillars | 20..37 hazards, 38 hazard_size, 39 bound |
+//   40.. (x y) of the 11 free bodies (vases, then the task object), 62-63 unused | 64.. their yaw, 75 unused |
+//   76.. their velocities (vx vy w) | 112 buttons | 124 catch | 128 last1,2 | 130 keepouts | 136 rebuild pose |
+//   140 ctrl_scale2.. | 152 robot extension
+// Everything a Point / Car step rewrites per step sits in groups 0-1; groups 2-3 only change when a goal moves.  The
+// quiet kernel reads the (x, y) run alone: yaw matters only to an env whose robot is within reach of something.
 constexpr int DEV_FLOATS = 192, DEV_GROUPS = DEV_FLOATS / 4;
-constexpr int DV_POS = 40, DV_VEL = 76, DG_HAZ = 5, DG_POS = 10, DG_PILLARS = 4, DG_BUTTONS = 28;
+constexpr int DV_XY = 40, DV_YAW = 64, DV_VEL = 76, DG_HAZ = 5, DG_XY = DV_XY / 4, DG_YAW = DV_YAW / 4, DG_PILLARS = 4, DG_BUTTONS = 28;
+constexpr int XY_GROUPS = 6, YAW_GROUPS = 3;
 __host__ __device__ constexpr int didx(int k) {
   return k < 6 ? k
        : k < 9 ? 136 + (k - 6)
-       : k < 12 ? k
-       : k < 14 ? k
+       : k < 11 ? 10 + (k - 9)
+       : k < 14 ? 12 + (k - 11)
        : k < 24 ? 140 + (k - 14)
        : k == 24 ? 38
-       : k < 27 ? 14 + (k - 25)
+       : k == 25 ? 15
+       : k == 26 ? 7
        : k < 32 ? 130 + (k - 27)
-       : k < 34 ? 6 + (k - 32)
+       : k < 34 ? 8 + (k - 32)
        : k < 38 ? 124 + (k - 34)
-       : k == 38 ? 8
+       : k == 38 ? 6
        : k < 41 ? 128 + (k - 39)
-       : k < 44 ? DV_POS + 30 + (k - 41)
+       : k < 43 ? DV_XY + 2 * SAG_MAX_VASES + (k - 41)
+       : k == 43 ? DV_YAW + SAG_MAX_VASES
        : k < 47 ? DV_VEL + 30 + (k - 44)
        : k < 65 ? 20 + (k - 47)
        : k < 69 ? 16 + (k - 65)
        : k < 81 ? 112 + (k - 69)
-       : k < 141 ? ((k - 81) % 6 < 3 ? DV_POS + 3 * ((k - 81) / 6) + (k - 81) % 6
-                                     : DV_VEL + 3 * ((k - 81) / 6) + (k - 81) % 6 - 3)
+       : k < 141 ? ((k - 81) % 6 < 2 ? DV_XY + 2 * ((k - 81) / 6) + (k - 81) % 6
+                    : (k - 81) % 6 == 2 ? DV_YAW + (k - 81) / 6
+                                        : DV_VEL + 3 * ((k - 81) / 6) + (k - 81) % 6 - 3)
        : k == 141 ? 39
        : k < 144 ? 150 + (k - 142)
        : 152 + (k - 144);
 }
-static_assert(didx(SAG_F_BUTTONS) == 112 && didx(SAG_F_VASES + 6 * 3 + 4) == DV_VEL + 10 && didx(SAG_F_BOX + 1) == DV_POS + 31 &&
+static_assert(didx(SAG_F_BUTTONS) == 112 && didx(SAG_F_VASES + 6 * 3 + 4) == DV_VEL + 10 && didx(SAG_F_BOX + 1) == DV_XY + 21 &&
               didx(SAG_F_HAZARDS) == 4 * DG_HAZ && didx(SAG_F_PILLARS) == 4 * DG_PILLARS, "device layout constants");
+static_assert(didx(SAG_F_VASES) == DV_XY && didx(SAG_F_VASES + 6 * 9 + 1) == DV_XY + 19 && didx(SAG_F_BOX) == DV_XY + 2 * SAG_MAX_VASES &&
+              didx(SAG_F_VASES + 2) == DV_YAW && didx(SAG_F_VASES + 6 * 9 + 2) == DV_YAW + 9 && didx(SAG_F_BOX + 2) == DV_YAW + SAG_MAX_VASES &&
+              DV_XY + 4 * XY_GROUPS == DV_YAW && DV_YAW + 4 * YAW_GROUPS == DV_VEL, "the (x, y) run and the yaw run of the free bodies");
+// every record float has a device float of its own, inside the device record
+constexpr bool didx_is_a_layout() {
+  bool used[DEV_FLOATS] = {};
+  for (int k = 0; k < SAG_REC_FLOATS; k++) {
+    const int d = didx(k);
+    if (d < 0 || d >= DEV_FLOATS || used[d]) return false;
+    used[d] = true;
+  }
+  return true;
+}
+static_assert(didx_is_a_layout(), "didx is injective over the record floats and stays below DEV_FLOATS");
 __host__ __device__ constexpr size_t saddr(int k, size_t N, size_t i) {
   return ((size_t)(didx(k) >> 2) * N + i) * 4 + (didx(k) & 3);
 }
@@ -707,8 +727,8 @@ __device__ inline unsigned long long cyc_wave_red(unsigned long long v, bool tak
 #include "sag_doggo.hpp"
 namespace sag {
 #define SF(k) S[saddr((k), (size_t)N, (size_t)i)]
-// by DEVICE index (free-body positions DV_POS + 3 k + c, velocities DV_VEL + 3 k + c with k = BOX_ID for
-// the task object): no record-to-device translation for run-time body indices
+// by DEVICE index (free-body positions DV_XY + 2 k + c and DV_YAW + k, velocities DV_VEL + 3 k + c with k = BOX_ID
+// for the task object): no record-to-device translation for run-time body indices
 #define SD(d) S[((size_t)((d) >> 2) * N + i) * 4 + ((d) & 3)]
 #define LP(base, k) lds[((base) + (k)) * WAVE + lane]
 #define POOL(d, c) lds[(LS_POOL + (d) * 6 + (c)) * WAVE + lane]
@@ -1040,8 +1060,8 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
   auto G4 = [&](int g) { return S4[(size_t)g * N + i]; };
   const bool use_hot = MODE == MODE_BUSY && p.hot != nullptr;
   const float4* __restrict__ H4 = use_hot ? reinterpret_cast<const float4*>(p.hot) + (size_t)i * HOT_GROUPS : nullptr;
-  // group g of this env: from the hot record (busy kernel; g < 14 covers 0-4 and the positions at
-  // 5 + (g - DG_POS)) or from the group-major state
+  // group g of this env: from the hot record (busy kernel; slots 0-4 = groups 0-4, 5-10 the (x, y) groups,
+  // 11-13 the yaw groups) or from the group-major state
   auto GH = [&](int g, int hslot) { return use_hot ? H4[hslot] : G4(g); };
   int4 iw;
   uint32_t tstate;
@@ -1062,8 +1082,8 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
   float yaw = gA.z;
   R.vx = gA.w; R.vy = gB.x; R.w = gB.y;
   R.ax = R.ay = R.aw = 0; R.dyn = 1;
-  const float gear = gC.y, damp = gC.z;
-  const float vsz = gD.z, psz = gD.w;
+  const float gear = gC.z, damp = gC.w;
+  const float vsz = gD.w, psz = gB.w;
   // car: wheel rates L, R; rear ball rate x, y, z (base axes); ball quaternion w, x, y, z
   float ext[9] = {0, 0, 0, 0, 0, 1, 0, 0, 0}, eacc[5] = {0, 0, 0, 0, 0};
   // (whole float4 groups: nine dword accesses at a 16-byte stride never cover a line, and the partial lines of the
@@ -1081,8 +1101,8 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       CPK(CP_TAIL) = ext_tail.y; CPK(CP_TAIL + 1) = ext_tail.z; CPK(CP_TAIL + 2) = ext_tail.w;
     }
   }
-  float goalx = gB.z, goaly = gB.w;
-  float last0 = gC.x;
+  float goalx = gC.x, goaly = gC.y;
+  float last0 = gB.z;
   float a0 = 0, a1 = 0, n0 = 0, n1 = 0;
   if (!p.observe_only) {
     if constexpr (!DOGGO) {
@@ -1091,22 +1111,45 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       if (p.noise) { const float2 z = reinterpret_cast<const float2*>(p.noise)[i]; n0 = z.x; n1 = z.y; }
     }
   }
+  // positions of the 11 free bodies: six (x, y) groups, then three yaw groups.  The quiet kernel leaves the yaw run alone:
+  // only an env whose robot is within reach of something needs it, and fetches it in the classification below.
+  const bool box_ctx = HAS_TBOX && p.has_box;
+  const int need_xy = box_ctx ? XY_GROUPS : (2 * capV + 3) / 4, need_yaw = box_ctx ? YAW_GROUPS : (capV + 3) / 4;
   {
-    // positions (x y yaw) of the 11 free bodies: 9 consecutive groups of the device record
-    float vpos[36];
-    const int need = HAS_TBOX && p.has_box ? 9 : (3 * capV + 3) / 4;
+    float vxy[4 * XY_GROUPS];
 #pragma unroll
-    for (int g = 0; g < 9; g++) {
+    for (int g = 0; g < XY_GROUPS; g++) {
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (g < need) v = GH(DG_POS + g, 5 + g);
-      vpos[4 * g] = v.x; vpos[4 * g + 1] = v.y; vpos[4 * g + 2] = v.z; vpos[4 * g + 3] = v.w;
+      if (g < need_xy) v = GH(DG_XY + g, 5 + g);
+      vxy[4 * g] = v.x; vxy[4 * g + 1] = v.y; vxy[4 * g + 2] = v.z; vxy[4 * g + 3] = v.w;
     }
 #pragma unroll
     for (int k = 0; k < SAG_MAX_VASES; k++)
-      if (k >= capV) { vpos[3 * k] = vpos[3 * k + 1] = vpos[3 * k + 2] = 0; }
-    if (!(HAS_TBOX && p.has_box)) { vpos[3 * BOX_ID] = vpos[3 * BOX_ID + 1] = vpos[3 * BOX_ID + 2] = 0; }
+      if (k >= capV) { vxy[2 * k] = vxy[2 * k + 1] = 0; }
+    if (!box_ctx) { vxy[2 * BOX_ID] = vxy[2 * BOX_ID + 1] = 0; }
 #pragma unroll
-    for (int k = 0; k < NBODY; k++) { LP(LS_X, k) = vpos[3 * k]; LP(LS_Y, k) = vpos[3 * k + 1]; LP(LS_YAW, k) = vpos[3 * k + 2]; }
+    for (int k = 0; k < NBODY; k++) { LP(LS_X, k) = vxy[2 * k]; LP(LS_Y, k) = vxy[2 * k + 1]; }
+  }
+  // the yaw rows of a lane from its three yaw groups (zero beyond the context's capacities, like x and y)
+  auto put_yaw = [&](const float4 (&yg)[YAW_GROUPS]) {
+    float vy_[4 * YAW_GROUPS];
+#pragma unroll
+    for (int g = 0; g < YAW_GROUPS; g++) { vy_[4 * g] = yg[g].x; vy_[4 * g + 1] = yg[g].y; vy_[4 * g + 2] = yg[g].z; vy_[4 * g + 3] = yg[g].w; }
+#pragma unroll
+    for (int k = 0; k < SAG_MAX_VASES; k++)
+      if (k >= capV) vy_[k] = 0;
+    if (!box_ctx) vy_[BOX_ID] = 0;
+#pragma unroll
+    for (int k = 0; k < NBODY; k++) LP(LS_YAW, k) = vy_[k];
+  };
+  if constexpr (!QUIET) {
+    float4 yg[YAW_GROUPS];
+#pragma unroll
+    for (int g = 0; g < YAW_GROUPS; g++) {
+      yg[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (g < need_yaw) yg[g] = GH(DG_YAW + g, 5 + XY_GROUPS + g);
+    }
+    put_yaw(yg);
   }
   // static colliders: pillars then buttons, in registers
   float stx[NSTAT], sty[NSTAT];
@@ -1172,8 +1215,8 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       philox4x32_10(c, p.key0, p.key1);
       box_muller(c[0], c[1], n0, n1);
     }
-    const float an = gC.w;
-    const float cs0 = gD.x, cs1 = gD.y;
+    const float an = gD.x;
+    const float cs0 = gD.y, cs1 = gD.z;
     ctrl0 = clampf(a0 + an * n0, -cs0, cs0);
     ctrl1 = clampf(a1 + an * n1, -cs1, cs1);
     // ---- CatchGoal.set_mocaps (tasks/catch_goal.py:20-31), time before the step ---
@@ -1314,7 +1357,8 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       LP(LS_X, k) = Wd.fb[k][0]; LP(LS_Y, k) = Wd.fb[k][1]; LP(LS_YAW, k) = Wd.fb[k][2];
       if (Wd.fb[k][3] != 0 || Wd.fb[k][4] != 0 || Wd.fb[k][5] != 0) awake |= 1u << k;
       if (!p.observe_only && live && !post) {
-        for (int c = 0; c < 3; c++) { SD(DV_POS + 3 * k + c) = Wd.fb[k][c]; SD(DV_VEL + 3 * k + c) = Wd.fb[k][3 + c]; }
+        SD(DV_XY + 2 * k) = Wd.fb[k][0]; SD(DV_XY + 2 * k + 1) = Wd.fb[k][1]; SD(DV_YAW + k) = Wd.fb[k][2];
+        for (int c = 0; c < 3; c++) SD(DV_VEL + 3 * k + c) = Wd.fb[k][3 + c];
       }
     }
   } else {
@@ -1751,8 +1795,8 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     }
     for (uint32_t m = dirty; m; m &= m - 1) {
       const int k = __ffs(m) - 1;
-      const int f = DV_POS + 3 * k, fv = DV_VEL + 3 * k;
-      SD(f) = LP(LS_X, k); SD(f + 1) = LP(LS_Y, k); SD(f + 2) = LP(LS_YAW, k);
+      const int f = DV_XY + 2 * k, fv = DV_VEL + 3 * k;
+      SD(f) = LP(LS_X, k); SD(f + 1) = LP(LS_Y, k); SD(DV_YAW + k) = LP(LS_YAW, k);
       const int d = dy.slot(k);
       if (d >= 0) { SD(fv) = POOL(d, 0); SD(fv + 1) = POOL(d, 1); SD(fv + 2) = POOL(d, 2); }
     }
@@ -1765,44 +1809,38 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
   //      touch the robot or move.  Reach of the robot within one step from the final state:
   //      |v| T + a_max T^2 (drive + contact-free dynamics only raise |v| by at most a_max T)
   bool busy_next = false;
-  if (!p.observe_only) {
-    const float T = p.nstep_table * h;
-    const float amax = CAR ? GRAV : 1.05f * gear * PT_FLIM / PT_MASS;
-    const float reach = sqrtf(R.vx * R.vx + R.vy * R.vy) * T + amax * T * T + 0.005f;
-    bool busy = awake != 0 || (HAS_TBOX && task == SAG_TASK_HAUL_BOX);
-    bool near_obj = false, near_static = false;   // (the kind: BUSY_CLASSES)
-    const bool moving = busy;
-    const float rr = my_bound + reach;
-    // Point: bounding circles first, then the footprint itself.  The robot is inside circle A (its sphere,
-    // r .1) and circle B (around the arrow box at +.1 along the heading, r .05 sqrt 2); within the step
-    // the origin travels <= reach and the heading turns <= dth (the yaw servo saturates at 3 rad/s).  A vase
-    // (sleeping here, else the env is busy anyway) can only be touched if its box comes within those radii:
-    // cb_contact needs the sphere centre closer than .1 to the box, bb_contact a vertex of one box inside the
-    // other, i.e. the box within .05 sqrt 2 of B's centre.  A third fewer envs pass than with circles alone.
-    constexpr bool FINE = !CAR && !DOGGO;
-    const float dth = (fmaxf(fabsf(R.w), 3.0f) + 1.0f) * T;
-    const float fa = 0.1f + reach, fb = 0.0707107f + reach + 0.1f * dth;
-    const float Bx = R.x + 0.1f * cy, By = R.y + 0.1f * sy;   // cy, sy: heading at the final state
-#pragma unroll 1
-    for (int k = 0; k < nV; k++) {
-      const float vx_ = LP(LS_X, k), vy_ = LP(LS_Y, k);
-      const float dx = vx_ - R.x, dyy = vy_ - R.y, rs = rr + vase_r;
-      if (dx * dx + dyy * dyy <= rs * rs) {
-        if constexpr (FINE) {
-          float sv, cv; sincosf(LP(LS_YAW, k), &sv, &cv);
-          auto box_d2 = [&](float px, float py) {   // squared distance of a point to the vase's box
-            const float wx = px - vx_, wy = py - vy_;
-            const float ex = fmaxf(fabsf(cv * wx + sv * wy) - vsz, 0.f), ey = fmaxf(fabsf(cv * wy - sv * wx) - vsz, 0.f);
-            return ex * ex + ey * ey;
-          };
-          busy |= box_d2(R.x, R.y) <= fa * fa || box_d2(Bx, By) <= fb * fb;
-        } else busy = true;
-      }
-    }
-    if (has_box) {
-      const float dx = LP(LS_X, BOX_ID) - R.x, dyy = LP(LS_Y, BOX_ID) - R.y, rs = rr + box_r;
-      near_obj = dx * dx + dyy * dyy <= rs * rs;
-    }
+  const float T = p.nstep_table * h;
+  const float amax = CAR ? GRAV : 1.05f * gear * PT_FLIM / PT_MASS;
+  const float reach = sqrtf(R.vx * R.vx + R.vy * R.vy) * T + amax * T * T + 0.005f;
+  const bool moving = awake != 0 || (HAS_TBOX && task == SAG_TASK_HAUL_BOX);
+  const float rr = my_bound + reach;
+  // Point: bounding circles first, then the footprint itself.  The robot is inside circle A (its sphere,
+  // r .1) and circle B (around the arrow box at +.1 along the heading, r .05 sqrt 2); within the step
+  // the origin travels <= reach and the heading turns <= dth (the yaw servo saturates at 3 rad/s).  A vase
+  // (sleeping here, else the env is busy anyway) can only be touched if its box comes within those radii:
+  // cb_contact needs the sphere centre closer than .1 to the box, bb_contact a vertex of one box inside the
+  // other, i.e. the box within .05 sqrt 2 of B's centre.  A third fewer envs pass than with circles alone.
+  constexpr bool FINE = !CAR && !DOGGO;
+  const float dth = (fmaxf(fabsf(R.w), 3.0f) + 1.0f) * T;
+  const float fa = 0.1f + reach, fb = 0.0707107f + reach + 0.1f * dth;
+  const float Bx = R.x + 0.1f * cy, By = R.y + 0.1f * sy;   // cy, sy: heading at the final state
+  // vase k inside the bounding circle: does its footprint come within reach?  (yaw row of the lane in LDS)
+  auto vase_fine = [&](int k, float vx_, float vy_) {
+    float sv, cv; sincosf(LP(LS_YAW, k), &sv, &cv);
+    auto box_d2 = [&](float px, float py) {   // squared distance of a point to the vase's box
+      const float wx = px - vx_, wy = py - vy_;
+      const float ex = fmaxf(fabsf(cv * wx + sv * wy) - vsz, 0.f), ey = fmaxf(fabsf(cv * wy - sv * wx) - vsz, 0.f);
+      return ex * ex + ey * ey;
+    };
+    return box_d2(R.x, R.y) <= fa * fa || box_d2(Bx, By) <= fb * fb;
+  };
+  auto object_near = [&]() {
+    if (!has_box) return false;
+    const float dx = LP(LS_X, BOX_ID) - R.x, dyy = LP(LS_Y, BOX_ID) - R.y, rs = rr + box_r;
+    return dx * dx + dyy * dyy <= rs * rs;
+  };
+  auto static_near = [&]() {
+    bool near_static = false;
 #pragma unroll 1
     for (int k = 0; k < n_static; k++) {
       if (k == capP) k = SAG_MAX_PILLARS;
@@ -1816,13 +1854,56 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
         near_static |= on && (dx * dx + dyy * dyy <= (fa + sr) * (fa + sr) || ex * ex + ey * ey <= (fb + sr) * (fb + sr));
       } else near_static |= on && dx * dx + dyy * dyy <= rs * rs;
     }
-    const bool near_vase = busy && !moving;    // (only the vase loop above has raised `busy` since)
-    busy |= near_obj || near_static;
+    return near_static;
+  };
+  // the busy bit of the next step, the kind byte (BUSY_CLASSES) and busy_next from the three findings
+  auto classified = [&](bool near_vase, bool near_obj, bool near_static) {
+    const bool busy = moving || near_vase || near_obj || near_static;
     const uint32_t kind = p.busy_kinds ? (uint32_t)near_obj | (uint32_t)near_static << 1 | (uint32_t)(near_vase || moving) << 2 : 0u;
     const uint32_t nbit = TS_BUSY_BIT << (p.phase ^ 1);
     tstate = busy ? (tstate | nbit) : (tstate & ~nbit);
     if (busy && live && p.kind) p.kind[i] = (uint8_t)kind;
     busy_next = busy;
+  };
+  if constexpr (!QUIET) {
+    if (!p.observe_only) {
+      bool near_vase = false;
+#pragma unroll 1
+      for (int k = 0; k < nV; k++) {
+        const float vx_ = LP(LS_X, k), vy_ = LP(LS_Y, k);
+        const float dx = vx_ - R.x, dyy = vy_ - R.y, rs = rr + vase_r;
+        if (dx * dx + dyy * dyy <= rs * rs) {
+          if constexpr (FINE) near_vase |= vase_fine(k, vx_, vy_);
+          else near_vase = true;
+        }
+      }
+      const bool near_obj = object_near(), near_static = static_near();
+      classified(near_vase, near_obj, near_static);
+    }
+  }
+  // Quiet kernel: the bounding circles need no yaw.  A lane with a vase inside the circle (the footprint test follows) or busy
+  // already by a static or the task object (its hot record carries the yaw) fetches its yaw groups here, under the hazard
+  // loads that follow: one round trip for both, and none for the yaw of the other lanes.
+  uint32_t circ_v = 0;   // vases inside the bounding circle
+  bool q_obj = false, q_static = false, q_cand = false;
+  float4 q_yaw[YAW_GROUPS];
+#pragma unroll
+  for (int g = 0; g < YAW_GROUPS; g++) q_yaw[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (QUIET) {
+    if (!p.observe_only) {
+#pragma unroll 1
+      for (int k = 0; k < nV; k++) {
+        const float dx = LP(LS_X, k) - R.x, dyy = LP(LS_Y, k) - R.y, rs = rr + vase_r;
+        if (dx * dx + dyy * dyy <= rs * rs) circ_v |= 1u << k;
+      }
+      q_obj = object_near(); q_static = static_near();
+      q_cand = live && (circ_v != 0 || q_obj || q_static || moving);
+      if (q_cand) {
+#pragma unroll
+        for (int g = 0; g < YAW_GROUPS; g++)
+          if (g < need_yaw) q_yaw[g] = G4(DG_YAW + g);
+      }
+    }
   }
 
   CYC(CY_WRITEBACK);
@@ -1842,6 +1923,21 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
 #pragma unroll
     for (int k = 0; k < SAG_MAX_HAZARDS; k++) { hzx[k] = k < capH ? hz[2 * k] : 0.f; hzy[k] = k < capH ? hz[2 * k + 1] : 0.f; }
     hsz = hz[18];
+  }
+  if constexpr (QUIET) {
+    if (!p.observe_only) {
+      bool near_vase = false;
+      if (q_cand) {
+        put_yaw(q_yaw);
+        if constexpr (FINE) {
+          for (uint32_t m = circ_v; m; m &= m - 1) {
+            const int k = __ffs(m) - 1;
+            near_vase |= vase_fine(k, LP(LS_X, k), LP(LS_Y, k));
+          }
+        } else near_vase = circ_v != 0;
+      }
+      classified(near_vase, q_obj, q_static);
+    }
   }
 
   // ---- PhysicsError branch (safe_adaptation_gym.py:73-75) -------------------------
@@ -2047,12 +2143,13 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     }
   }
   if constexpr (!DOGGO) {
-    // groups 1 (vy w goal) and 2 (last0 gear damp noise) as whole float4: full lines instead of
-    // scattered dwords.  A failed env (PhysicsError) keeps its old goal and `last`.
+    // group 1 (vy w last0 pillar_size) as a whole float4: full lines instead of scattered dwords.  Group 2 (goal gear
+    // damp) only where the goal moved: a resample, or CatchGoal's orbit.  A failed env (PhysicsError) keeps its old
+    // goal and `last`.
     if (!p.observe_only && live) {
       float4* __restrict__ W4 = reinterpret_cast<float4*>(S);
-      W4[(size_t)1 * N + i] = make_float4(R.vy, R.w, bad ? gB.z : goalx, bad ? gB.w : goaly);
-      W4[(size_t)2 * N + i] = make_float4(bad ? gC.x : last0, gC.y, gC.z, gC.w);
+      W4[(size_t)1 * N + i] = make_float4(R.vy, R.w, bad ? gB.z : last0, gB.w);
+      if (!bad && (need_goal || task == SAG_TASK_CATCH_GOAL)) W4[(size_t)2 * N + i] = make_float4(goalx, goaly, gC.z, gC.w);
     }
   }
   if (!p.observe_only && live) I[iaddr(DI_TSTATE, (size_t)N, (size_t)i)] = (int32_t)tstate;
@@ -2062,17 +2159,18 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     if (p.hot && busy_next && live && !p.observe_only) {
       float4* __restrict__ Hw = reinterpret_cast<float4*>(p.hot) + (size_t)i * HOT_GROUPS;
       Hw[0] = make_float4(R.x, R.y, yaw, R.vx);
-      Hw[1] = make_float4(R.vy, R.w, bad ? gB.z : goalx, bad ? gB.w : goaly);
-      Hw[2] = make_float4(bad ? gC.x : last0, gC.y, gC.z, gC.w);
+      Hw[1] = make_float4(R.vy, R.w, bad ? gB.z : last0, gB.w);
+      Hw[2] = make_float4(bad ? gC.x : goalx, bad ? gC.y : goaly, gC.z, gC.w);
       Hw[3] = gD;
       Hw[4] = make_float4(stx[0], sty[0], stx[1], sty[1]);
 #pragma unroll
-      for (int g = 0; g < 9; g++) {
+      for (int g = 0; g < XY_GROUPS + YAW_GROUPS; g++) {
         float v[4];
 #pragma unroll
         for (int c = 0; c < 4; c++) {
-          const int f = 4 * g + c, k = f / 3, comp = f % 3;   // float f of the position block = body k, x / y / yaw
-          v[c] = k < NBODY ? lds[((comp == 0 ? LS_X : (comp == 1 ? LS_Y : LS_YAW)) + k) * WAVE + lane] : 0.f;
+          // slots 5-10: float f of the (x, y) run = body f / 2, x / y; slots 11-13: float f of the yaw run = body f
+          const int f = 4 * (g < XY_GROUPS ? g : g - XY_GROUPS) + c, k = g < XY_GROUPS ? f / 2 : f;
+          v[c] = k < NBODY ? lds[((g < XY_GROUPS ? (f % 2 == 0 ? LS_X : LS_Y) : LS_YAW) + k) * WAVE + lane] : 0.f;
         }
         Hw[5 + g] = make_float4(v[0], v[1], v[2], v[3]);
       }
@@ -2379,10 +2477,10 @@ __global__ __launch_bounds__(WAVE, 1) void k_step_doggo_post(StepArgs p) {
 #endif
 template <int ROBOT, bool HAS_BTN, bool HAS_TBOX>
 __global__ __launch_bounds__(WAVE, ROBOT == SAG_ROBOT_CAR ? SAG_CAR_QUIET_MIN_WAVES : SAG_QUIET_MIN_WAVES) void k_step_quiet(StepArgs p) {
-  // positions (x, y) of the free bodies + the observation staging (one chunk's tile, or the whole row where it fits:
+  // positions (x, y; yaw only of the lanes the classification fetches it for) of the free bodies + the observation staging (one chunk's tile, or the whole row where it fits:
   // obs_whole_rows); no dynamic pool.  The launch pads it to quiet_lds_total with dynamic LDS that nobody touches.
   constexpr int QSLOTS = quiet_lds_rows(ROBOT, HAS_BTN, HAS_TBOX);
-  static_assert(QSLOTS >= LS_YAW + NBODY, "the yaw rows written at load time must stay in bounds");
+  static_assert(QSLOTS >= LS_YAW + NBODY, "the yaw rows a lane within reach of something writes (classification) must stay in bounds");
   static_assert(QSLOTS * WAVE * (int)sizeof(float) <= quiet_lds_total(ROBOT), "the quiet array stays inside the footprint of its launch");
   __shared__ float lds[QSLOTS * WAVE];
   const int lane = threadIdx.x, base = blockIdx.x * WAVE, gi = base + lane;
@@ -2508,7 +2606,7 @@ __device__ inline void hot_refresh_env(const float* __restrict__ S, const int32_
   const float4* S4 = reinterpret_cast<const float4*>(S);
   float4* H = reinterpret_cast<float4*>(hot) + i * HOT_GROUPS;
   for (int g = 0; g < 5; g++) H[g] = S4[(size_t)g * N + i];
-  for (int g = 0; g < 9; g++) H[5 + g] = S4[(size_t)(DG_POS + g) * N + i];
+  for (int g = 0; g < XY_GROUPS + YAW_GROUPS; g++) H[5 + g] = S4[(size_t)(DG_XY + g) * N + i];   // (x, y) groups, then yaw
   const int4 iw = reinterpret_cast<const int4*>(I + ipad((size_t)N))[i];
   H[14] = make_float4(__int_as_float(iw.x), __int_as_float(iw.y), __int_as_float(iw.z), __int_as_float(iw.w));
   H[15] = make_float4(__int_as_float(I[i]), 0.f, 0.f, 0.f);

@@ -1076,7 +1076,8 @@ __global__ __launch_bounds__(32 * DC_EPW) void k_doggo_physics(StepArgs p, doubl
     const int k = u;
     const bool isb = k == BOX_ID, on = isb ? W.has_box : k < W.nV;
     for (int c = 0; c < 3; c++) {
-      E.wfb[k][c] = on ? S[((size_t)((DV_POS + 3 * k + c) >> 2) * N + i) * 4 + ((DV_POS + 3 * k + c) & 3)] : 0.f;
+      const int dp = c < 2 ? DV_XY + 2 * k + c : DV_YAW + k;   // device float of position component c (sag_device.hpp didx)
+      E.wfb[k][c] = on ? S[((size_t)(dp >> 2) * N + i) * 4 + (dp & 3)] : 0.f;
       E.wfb[k][3 + c] = on ? S[((size_t)((DV_VEL + 3 * k + c) >> 2) * N + i) * 4 + ((DV_VEL + 3 * k + c) & 3)] : 0.f;
       E.wfb[k][6 + c] = 0.f;
     }
@@ -1458,7 +1459,8 @@ __global__ __launch_bounds__(32 * DC_EPW) void k_doggo_physics(StepArgs p, doubl
         const bool isb = u == BOX_ID;
         if (isb ? W.has_box : u < W.nV)
           for (int c = 0; c < 3; c++) {
-            S[((size_t)((DV_POS + 3 * u + c) >> 2) * N + gi) * 4 + ((DV_POS + 3 * u + c) & 3)] = E.wfb[u][c];
+            const int dp = c < 2 ? DV_XY + 2 * u + c : DV_YAW + u;
+            S[((size_t)(dp >> 2) * N + gi) * 4 + (dp & 3)] = E.wfb[u][c];
             S[((size_t)((DV_VEL + 3 * u + c) >> 2) * N + gi) * 4 + ((DV_VEL + 3 * u + c) & 3)] = E.wfb[u][3 + c];
           }
       }
