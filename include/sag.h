@@ -446,6 +446,8 @@ int sag_reset_device(sag_ctx* ctx, int32_t first_episode, int32_t episode0, cons
  * step -> episode bookkeeping -> masked reset of the envs that ended -> step, without a host wait or copy:
  *   sag_step_device(..., d_obs, d_reward, d_cost, d_done, d_goal_met);
  *   sag_episode_track_device(ctx, d_reward, d_cost, d_done, d_goal_met, max_steps, d_ended, d_episode);
+ *   sag_copy_rows_device(ctx, d_ended, obs_dim * 4, d_obs, d_final);   (optional: the final observations, before the
+ *                                                                        reset overwrites the rows of the envs that ended)
  *   sag_reset_device_async(ctx, d_ended, d_obs);
  *
  * sag_reset_device_async: stream-ordered form of sag_reset_device(first_episode = 0): needs sag_set_tasks and an installed
@@ -472,6 +474,11 @@ int sag_episode_track_device(sag_ctx* ctx, const float* d_reward, const uint8_t*
                              const uint8_t* d_goal_met, int32_t max_steps, uint8_t* d_ended, float* d_episode);
 /* Zero the accumulators of the masked envs (NULL: all), stream-ordered. */
 int sag_episode_clear(sag_ctx* ctx, const uint8_t* d_mask);
+/* For the envs with a non-zero byte of d_mask ([n_envs] device bytes; NULL: every env) copy row i
+ * (row_bytes bytes) of d_src to row i of d_dst.  Stream-ordered, returns without waiting, no host copy,
+ * no timing events.  SAG_ERR_ARG with nothing enqueued: NULL d_src / d_dst, row_bytes <= 0 or not a
+ * multiple of 16, a pointer that is not 16-byte aligned, d_src == d_dst. */
+int sag_copy_rows_device(sag_ctx* ctx, const uint8_t* d_mask, int32_t row_bytes, const void* d_src, void* d_dst);
 
 /* ---- fork on the device (throughput mode) -------------------------------------------------------
  * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`

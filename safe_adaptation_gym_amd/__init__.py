@@ -27,7 +27,8 @@ def make(robot_name: str,
          device_buffers: bool = False,
          device_reset: bool = False,
          time_limit: Optional[int] = None,
-         auto_reset: bool = False):
+         auto_reset: bool = False,
+         final_observation: bool = False):
   from safe_adaptation_gym_amd.benchmark import ROBOTS_BASENAMES, TASKS
   from safe_adaptation_gym_amd.envs import BatchedSafeAdaptationGym
   env = BatchedSafeAdaptationGym(
@@ -41,6 +42,7 @@ def make(robot_name: str,
       device_reset=device_reset,
       time_limit=time_limit,
       auto_reset=auto_reset,
+      final_observation=final_observation,
       render_lidars_and_collision=render_lidar_and_collision,
       render_options=render_options)
   env.seed(seed)

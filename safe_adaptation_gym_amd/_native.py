@@ -35,7 +35,7 @@ EXPORTS = [
     'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_render_rows_device', 'sag_render_envs', 'sag_render_aux', 'sag_render_aux_device', 'sag_debug_doggo_coop',
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
-    'sag_episode_clear', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
+    'sag_episode_clear', 'sag_copy_rows_device', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
     'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device'
 ]
 
@@ -119,6 +119,7 @@ def load():
   lib.sag_reset_device_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
   lib.sag_episode_track_device.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp]
   lib.sag_episode_clear.argtypes = [vp, vp]
+  lib.sag_copy_rows_device.argtypes = [vp, vp, C.c_int32, vp, vp]
   lib.sag_fork_device.argtypes = [vp, vp, vp, C.c_int32]
   lib.sag_fork_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
   lib.sag_wait_for.argtypes = [vp, vp]
@@ -473,6 +474,12 @@ class Context:
 
   def episode_clear(self, d_mask=None):
     self._check(self.lib.sag_episode_clear(self.h, d_mask), 'sag_episode_clear')
+
+  def copy_rows(self, d_mask, row_bytes, d_src, d_dst):
+    """sag_copy_rows_device: row i (row_bytes bytes, a multiple of 16) of d_src -> row i of d_dst for the envs with a non-zero
+    byte of d_mask (device pointer of [n_envs] bytes; None: every env), enqueued on the context stream - no wait, no host
+    copy.  The other rows of d_dst are not written."""
+    self._check(self.lib.sag_copy_rows_device(self.h, d_mask, int(row_bytes), d_src, d_dst), 'sag_copy_rows_device')
 
   def fork_device(self, d_src, source=None, same_stream=False, flags=None):
     """sag_fork_device: env i takes the complete state of env d_src[i] of `source` (a Context on the same device; default:

@@ -937,6 +937,19 @@ int sag_episode_clear(sag_ctx* c, const uint8_t* d_mask) {
   return SAG_OK;
 }
 
+int sag_copy_rows_device(sag_ctx* c, const uint8_t* d_mask, int32_t row_bytes, const void* d_src, void* d_dst) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d_src || !d_dst || d_src == d_dst) return fail(c, SAG_ERR_ARG, "sag_copy_rows_device: d_src and d_dst must be two buffers, neither NULL");
+  if (row_bytes <= 0 || (row_bytes & 15)) return fail(c, SAG_ERR_ARG, "sag_copy_rows_device: row_bytes %d is not a positive multiple of 16", row_bytes);
+  if ((reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst)) & 15)
+    return fail(c, SAG_ERR_ARG, "sag_copy_rows_device: d_src and d_dst must be 16-byte aligned");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(k_save_rows, dim3((c->N + WAVE - 1) / WAVE), dim3(WAVE), 0, c->stream, c->N, d_mask, row_bytes / 16,
+                     reinterpret_cast<const float4*>(d_src), reinterpret_cast<float4*>(d_dst));
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
 // decide -> state -> layout rows -> int words and what hangs on an env, on dst's stream.  Between two contexts the source's
 // stream is joined first (what is enqueued there, a step for one, is seen) and waits for the copy afterwards (its next step
 // cannot overtake the reads).

@@ -1,5 +1,6 @@
 // sag_rollout.hpp - what closes the rollout loop on the context stream after a device step, without a host decision:
 //   k_episode_track    return / cost / length / goals met per env and the "ended" byte (sag_episode_track_device)
+//   k_save_rows        the rows of the envs that ended, kept before the reset overwrites them (sag_copy_rows_device)
 //   k_reset_commit     the install of a masked device reset, env by env (sag_reset_device_async)
 //   k_observe_rows     Point / Car: the first observation of the new episodes, formed for the listed envs only
 //   k_copy_rows        Doggo: the listed rows of a whole-batch observation
@@ -35,6 +36,51 @@ __global__ __launch_bounds__(256) void k_episode_track(int N, const float* __res
 __global__ __launch_bounds__(256) void k_episode_clear(int N, const uint8_t* __restrict__ mask, float4* __restrict__ acc) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < N && mask[i]) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// For the envs with a non-zero mask byte (mask == nullptr: every env), row i of src -> row i of dst, Q float4 pieces each.
+// One wavefront per 64 consecutive envs.  A wavefront whose 64 mask bytes are zero has read them and nothing else.  Otherwise
+// the set lanes write their lane numbers to tab[] in rank order and all 64 lanes walk the count * Q pieces of those rows:
+// piece p is piece p % Q of the row of tab[p / Q] - kept per lane as (e, q) = (p / Q, p % Q) and advanced by 64 pieces at a
+// time, so no product can overflow for any row size.  Under a full mask tab[e] = e and consecutive lanes touch consecutive 16
+// bytes of one 64-row span.  SAVE_PIECES pieces per lane are loaded before the first is stored: with 32 wavefronts per CU
+// that is 128 KiB in flight per CU, where one piece per lane (32 KiB) would not cover the memory latency at the copy rate.
+constexpr int SAVE_PIECES = 4;
+__global__ __launch_bounds__(WAVE) void k_save_rows(int N, const uint8_t* __restrict__ mask, int Q, const float4* __restrict__ src,
+                                                     float4* __restrict__ dst) {
+  __shared__ int tab[WAVE];
+  const int lane = threadIdx.x;
+  const size_t row0 = (size_t)blockIdx.x * WAVE, i = row0 + lane;
+  const bool set = i < (size_t)N && (!mask || mask[i] != 0);
+  const uint64_t b = __ballot(set);
+  if (b == 0) return;
+  if (set) tab[__popcll(b & ((1ull << lane) - 1))] = lane;
+  __syncthreads();
+  const int count = __popcll(b), de = WAVE / Q, dq = WAVE % Q;
+  int e = lane / Q, q = lane % Q;
+  while (e < count) {
+    size_t at[SAVE_PIECES];
+    int n = 0;   // pieces of this pass that exist for this lane
+#pragma unroll
+    for (int u = 0; u < SAVE_PIECES; u++) {
+      if (e < count) n = u + 1;
+      at[u] = (row0 + (size_t)tab[min(e, count - 1)]) * (size_t)Q + (size_t)q;
+      e += de;
+      q += dq;
+      if (q >= Q) { q -= Q; e++; }
+    }
+    if (n == SAVE_PIECES) {   // no branch between the loads: they are issued back to back, then the stores
+      float4 v[SAVE_PIECES];
+#pragma unroll
+      for (int u = 0; u < SAVE_PIECES; u++) v[u] = src[at[u]];
+#pragma unroll
+      for (int u = 0; u < SAVE_PIECES; u++) dst[at[u]] = v[u];
+    } else {                  // the lane's last pass
+#pragma unroll
+      for (int u = 0; u < SAVE_PIECES - 1; u++)
+        if (u < n) dst[at[u]] = src[at[u]];
+    }
+  }
 }
 
 struct CommitArgs {

@@ -52,7 +52,7 @@ class BatchedSafeAdaptationGym:
 
   def __init__(self, robot_base, n_envs=1, rgb_observation=False, config=None, devices=None,
                parity_rng=False, device_seed=None, render_lidars_and_collision=False, render_options=None,
-               device_buffers=False, device_reset=False, time_limit=None, auto_reset=False):
+               device_buffers=False, device_reset=False, time_limit=None, auto_reset=False, final_observation=False):
     # rgb_observation: the observation is the robot camera's 64 x 64 x 3 uint8 image
     # (safe_adaptation_gym.py:122-126,148-149), ray-cast on the device
     self._rgb_observation = bool(rgb_observation)
@@ -75,12 +75,13 @@ class BatchedSafeAdaptationGym:
     if self.device_reset and self.parity_rng:
       raise ValueError('device_reset: parity_rng reproduces the reference\'s host MT19937 layout stream')
     # time_limit / auto_reset: the episode loop on the contexts' streams (sag_episode_track_device after every step, then
-    # sag_reset_device_async of the envs that ended); see step()
-    if (time_limit is not None or auto_reset) and self._rgb_observation:
+    # sag_reset_device_async of the envs that ended); final_observation: the observation rows of the envs that ended are
+    # saved (sag_copy_rows_device) before that reset overwrites them; see step()
+    if (time_limit is not None or auto_reset or final_observation) and self._rgb_observation:
       # (the constructor's refusal is kept as it was; the loop itself handles images: episode_loop())
       raise ValueError('time_limit / auto_reset with rgb_observation is not supported by make(): call '
                        'env.episode_loop(time_limit, auto_reset) on the env')
-    self._set_episode_loop(time_limit, auto_reset)
+    self._set_episode_loop(time_limit, auto_reset, final_observation)
     self._last_obs = None   # device_reset, host buffers: what the last step() returned (rows kept by a masked reset)
     self._mask_bufs = None  # device_reset: per-shard device copies of a host reset mask
     self._fork_bufs = None  # fork(): per-shard device copies of a host source-index array
@@ -111,9 +112,12 @@ class BatchedSafeAdaptationGym:
     self._observation_space = None
     self._reward_dim = 1
 
-  def _set_episode_loop(self, time_limit, auto_reset):
+  def _set_episode_loop(self, time_limit, auto_reset, final_observation=False):
     self.time_limit = None if time_limit is None else int(time_limit)
     self.auto_reset = bool(auto_reset)
+    self.final_observation = bool(final_observation)
+    if self.final_observation and not self.auto_reset:
+      raise ValueError('final_observation needs auto_reset=True: without it the observation a step returns is the final one')
     self._track = self.time_limit is not None or self.auto_reset
     if self._track:
       if self.parity_rng:
@@ -123,16 +127,16 @@ class BatchedSafeAdaptationGym:
       if self.time_limit is not None and self.time_limit <= 0:
         raise ValueError(f'time_limit must be positive, not {time_limit}')
 
-  def episode_loop(self, time_limit=None, auto_reset=False):
-    """Turns on what make(..., time_limit=, auto_reset=) turns on - the episode tracker and the stream-ordered reset of the
-    envs that ended, see step() - on an env that exists.  This is how an rgb_observation env gets them: make() refuses that
-    combination, the loop does not.  Same requirements (device_buffers, device_reset, no parity_rng), ValueError otherwise
+  def episode_loop(self, time_limit=None, auto_reset=False, final_observation=False):
+    """Turns on what make(..., time_limit=, auto_reset=, final_observation=) turns on - the episode tracker, the stream-ordered
+    reset of the envs that ended and the copy of their final observations, see step() - on an env that exists.  This is how
+    an rgb_observation env gets them: make() refuses that combination, the loop does not.  Same requirements (device_buffers, device_reset, no parity_rng), ValueError otherwise
     and the env stays as it was; to be called before the first reset() / step() (the device buffers are laid out then)."""
     if self._dev is not None:
       raise ValueError('episode_loop(): call it before the first reset() / step()')
-    old = self.time_limit, self.auto_reset
+    old = self.time_limit, self.auto_reset, self.final_observation
     try:
-      self._set_episode_loop(time_limit, auto_reset)
+      self._set_episode_loop(time_limit, auto_reset, final_observation)
     except ValueError:
       self._set_episode_loop(*old)
       raise
@@ -401,13 +405,21 @@ class BatchedSafeAdaptationGym:
     last finished episode (rows of envs that have not finished one are zero).
     auto_reset=True (time_limit=None: no limit): after the tracker the envs that ended are reset on the stream, and
     their rows of the returned observation are the FIRST observation of the new episode; reward, cost and goal_met are
-    the final transition's.  The final observation of an ended episode is not kept: a learner that needs it steps
-    without auto_reset and calls reset(mask=done, sync=False) itself after reading it.
+    the final transition's.
+    final_observation=True (needs auto_reset): between the tracker and the reset the observation rows of the envs that ended
+    are copied on the stream (sag_copy_rows_device), and info['final_observation'] is a device view of that buffer, shaped as
+    `obs` (a list of views, one per shard, when the batch is sharded).  The rows of envs whose `done` is non-zero in this
+    step hold the observation of the state the final transition reached - what a learner bootstraps from after a
+    truncation.  Every other row keeps what it held: zeros until the env first ends an episode, then the final observation
+    of its most recent one (as info['episode']).  The view is overwritten by the next step.  An env whose resampling fails
+    keeps its state: its observation row and its final row are then the same.
 
     rgb_observation=True (the loop turned on with episode_loop()): `obs` is the image view [N, 64, 64, 3] uint8 and the
     same contract holds.  With time_limit alone the stream runs step, render, tracker: the image is the final observation.
     With auto_reset it runs step, tracker, reset of the ended envs (no vector observation is formed), then one render of
-    the whole batch: each env is rendered once per step and an ended env's image is the first of its new episode."""
+    the whole batch: each env is rendered once per step and an ended env's image is the first of its new episode.  With
+    final_observation the envs that ended, and only they, are rendered a second time: before the reset, into their rows of
+    info['final_observation'] ([N, 64, 64, 3] uint8, sag_render_rows_device)."""
     if self.device_buffers:
       return self._step_device(action, sync)
     a = np.asarray(action, np.float32).reshape(self.n_envs, self.robot.nu)
@@ -452,6 +464,10 @@ class BatchedSafeAdaptationGym:
           c.dev_upload(b['episode'], np.zeros((n, 4), np.float32))
         if self._rgb_observation:
           b['img'] = c.dev_alloc(n * 64 * 64 * 3)
+        if self.final_observation:
+          shape, dtype = ((n, 64, 64, 3), np.uint8) if self._rgb_observation else ((n, od), np.float32)
+          b['final'] = c.dev_alloc(int(np.prod(shape)) * np.dtype(dtype).itemsize)
+          c.dev_upload(b['final'], np.zeros(shape, dtype))
         self._dev.append(b)
     return self._dev
 
@@ -493,6 +509,11 @@ class BatchedSafeAdaptationGym:
         c.render_rgb_device(b['img'])
       if self._track:
         c.episode_track(b['rew'], b['cost'], b['done'], b['met'], self.time_limit or 0, b['ended'], b['episode'])
+        if self.final_observation:   # (before the reset: the state, and the observation rows, of the final transition)
+          if rgb:
+            c.render_rows_device(b['ended'], b['final'])
+          else:
+            c.copy_rows(b['ended'], self.robot.obs_dim * 4, b['obs'], b['final'])
         if self.auto_reset:   # every env is rendered once, after the resets: an ended env shows its new episode
           c.reset_device_async(b['ended'], None if rgb else b['obs'])
           if rgb:
@@ -511,6 +532,9 @@ class BatchedSafeAdaptationGym:
     ended = [A(c, b['ended'].value, (e - s,), np.uint8) for c, b, (s, e) in zip(self._ctx, bufs, self._ranges)]
     episode = [A(c, b['episode'].value, (e - s, 4), np.float32) for c, b, (s, e) in zip(self._ctx, bufs, self._ranges)]
     info.update(terminated=pick(2), episode=episode[0] if one else episode)
+    if self.final_observation:
+      final = [A(c, b['final'].value, o[0].shape, o[0].dtype) for c, b, o in zip(self._ctx, bufs, outs)]
+      info['final_observation'] = final[0] if one else final
     return pick(0), pick(1), ended[0] if one else ended, info
 
   def wait(self):
