@@ -480,6 +480,71 @@ int sag_episode_clear(sag_ctx* ctx, const uint8_t* d_mask);
  * multiple of 16, a pointer that is not 16-byte aligned, d_src == d_dst. */
 int sag_copy_rows_device(sag_ctx* ctx, const uint8_t* d_mask, int32_t row_bytes, const void* d_src, void* d_dst);
 
+/* ---- a time-major rollout buffer on the context stream (throughput mode) -------------------------
+ * The step takes arbitrary device pointers, so T steps of experience need no copy: step t writes plane t of [T][pitch]...
+ * arrays (pitch >= n_envs envs per plane), and per step
+ *   sag_step_device(ctx, actions[t], NULL, -1, obs[t + 1], reward[t], cost[t], terminated[t], goal_met[t]);
+ *   sag_episode_track_device(ctx, reward[t], cost[t], terminated[t], goal_met[t], max_steps, ended[t], episode[t]);
+ *   sag_append_rows_device(ctx, ended[t], obs_dim * 4, obs[t + 1], d_store, capacity, d_count, t == 0, slot[t]);
+ *   sag_reset_device_async(ctx, ended[t], obs[t + 1]);
+ * keeps the final observations of the episodes that ended - the few rows a learner bootstraps from after a truncation -
+ * compacted in d_store; after T steps sag_gae_device turns stored rewards, costs, `ended` bytes and the learner's values into
+ * advantages and returns of both channels.  Both calls are enqueued on the context stream and return without waiting; they copy
+ * nothing to the host, record no timing events and need no installed layout.
+ *
+ * sag_append_rows_device: the compacting sibling of sag_copy_rows_device.  For each env i with a non-zero byte of d_mask
+ * ([n_envs] device bytes, required) row i of d_src (row_bytes bytes, a multiple of 16; both buffers 16-byte aligned) is
+ * appended to d_store ([capacity][row_bytes]) at slot s, and d_slot[i] = s.  d_slot ([n_envs] int32) is written for EVERY env:
+ * -1 where the mask byte is zero or the row did not fit.  d_count is one device int32, the number of slots claimed so far: it
+ * may exceed capacity - a claim at or beyond capacity writes no row and gets slot -1 -, so min(count, capacity) rows of the
+ * store are valid and max(0, count - capacity) rows were dropped.  restart != 0 sets the counter to zero on the stream before
+ * the append.  Claiming costs one returning atomic add per wavefront (64 consecutive envs) that has any set lane: inside such
+ * a group of 64 envs the slots ascend with the env index; the order BETWEEN groups is unspecified and may differ from run to
+ * run - d_slot is the only map from envs to rows.  Rows of the store that no claim reached are not written.
+ * SAG_ERR_ARG with nothing enqueued: a NULL pointer, row_bytes <= 0 or not a multiple of 16, d_src or d_store not 16-byte
+ * aligned, d_src == d_store, capacity < 1, d_count or d_slot not 4-byte aligned. */
+int sag_append_rows_device(sag_ctx* ctx, const uint8_t* d_mask, int32_t row_bytes, const void* d_src, void* d_store,
+                           int32_t capacity, int32_t* d_count, int32_t restart, int32_t* d_slot);
+
+/* sag_gae_device: generalised advantage estimation for the reward channel and, when d_cvalue is given, the cost channel.
+ * Every array is a device array; time-major ones have `pitch` >= n_envs elements per step, of which the first n_envs are
+ * read or written (the rest is never touched).
+ *   d_reward [T][pitch][2] f32 (column 0 is used; 8-byte aligned)     d_cost [T][pitch] u8      d_ended [T][pitch] u8: 0, 1
+ *   (terminated) or 2 (truncated), as sag_episode_track_device writes it      d_value, d_cvalue [T + 1][pitch] f32 (d_cvalue
+ *   NULL: no cost channel)      d_slot [T][pitch] int32 or NULL: the slots of sag_append_rows_device      d_final_value,
+ *   d_final_cvalue [capacity] f32 or NULL: the learner's values of the rows of that store
+ *   outputs d_adv, d_ret, d_cadv, d_cret [T][pitch] f32; the cost outputs are required exactly when d_cvalue is given.
+ * Per env, carry = 0 and t = T - 1 ... 0, in fp32 with every operation rounded on its own (no fused multiply-add), and
+ * gl = gamma * lam rounded once:
+ *   e = ended[t]
+ *   e == 0:                                                            nv = value[t + 1]            (carry stays)
+ *   e == 2, d_slot and d_final_value given, 0 <= slot[t] < capacity:   nv = final_value[slot[t]];   carry = 0
+ *   otherwise (terminated, or truncated without a kept final row):     nv = 0;                      carry = 0
+ *   q = gamma * nv;  s = r + q;  delta = s - value[t];  p = gl * carry;  A = delta + p;  ret = A + value[t]
+ *   adv[t] = A;  ret[t] = ret;  carry = A
+ * with r = reward[t][0].  The cost channel is the same recurrence with r = (cost[t] != 0 ? 1 : 0), d_cvalue, d_final_cvalue,
+ * cost_gamma and cost_lam.  value[t + 1] of an env that ended at t belongs to the new episode and is not read for it.
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc or required array, T < 1, pitch < n_envs, one of the four gammas / lambdas
+ * outside [0, 1] or not finite, d_reward not 8-byte or another array not 4-byte aligned, cost outputs without d_cvalue or
+ * d_cvalue without both cost outputs, d_slot with capacity < 1. */
+typedef struct sag_gae_desc {
+  int32_t T, pitch, capacity, reserved;
+  float gamma, lam, cost_gamma, cost_lam;
+  const float* d_reward;
+  const uint8_t* d_cost;
+  const uint8_t* d_ended;
+  const float* d_value;
+  const float* d_cvalue;
+  const int32_t* d_slot;
+  const float* d_final_value;
+  const float* d_final_cvalue;
+  float* d_adv;
+  float* d_ret;
+  float* d_cadv;
+  float* d_cret;
+} sag_gae_desc;
+int sag_gae_device(sag_ctx* ctx, const sag_gae_desc* desc);
+
 /* ---- fork on the device (throughput mode) -------------------------------------------------------
  * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`
  * itself (a fork inside a batch) or another one, of any n_envs (a few real envs feeding many planner envs; a second context

@@ -11,6 +11,9 @@ def __getattr__(name):
   if name == 'ShootingPlanner':   # sag.ShootingPlanner(env, ...): a constrained CEM planner on the device (planner.py)
     from safe_adaptation_gym_amd.planner import ShootingPlanner
     return ShootingPlanner
+  if name == 'RolloutBuffer':   # sag.RolloutBuffer(env, steps): time-major storage written in place, final rows, GAE (rollout_buffer.py)
+    from safe_adaptation_gym_amd.rollout_buffer import RolloutBuffer
+    return RolloutBuffer
   raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 

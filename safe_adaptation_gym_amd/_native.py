@@ -36,7 +36,7 @@ EXPORTS = [
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
     'sag_episode_clear', 'sag_copy_rows_device', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
-    'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device'
+    'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device'
 ]
 
 
@@ -57,6 +57,14 @@ class WorldConfig(C.Structure):
                                          'vases_keepout', 'pillars_keepout',
                                          'robot_ctrl_range_scale', 'action_noise', 'max_bound')] + [
                                              ('random_bound', C.c_int32), ('reserved', C.c_int32)]
+
+
+class GaeDesc(C.Structure):
+  """sag_gae_desc (include/sag.h)."""
+  _fields_ = [(k, C.c_int32) for k in ('T', 'pitch', 'capacity', 'reserved')] + [
+      (k, C.c_float) for k in ('gamma', 'lam', 'cost_gamma', 'cost_lam')] + [
+          (k, C.c_void_p) for k in ('d_reward', 'd_cost', 'd_ended', 'd_value', 'd_cvalue', 'd_slot', 'd_final_value',
+                                    'd_final_cvalue', 'd_adv', 'd_ret', 'd_cadv', 'd_cret')]
 
 
 _lib = None
@@ -128,6 +136,8 @@ def load():
   lib.sag_plan_refit_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, vp, vp, vp, vp]
   lib.sag_plan_shift_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_float]
   lib.sag_plan_clear_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_float]
+  lib.sag_append_rows_device.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp]
+  lib.sag_gae_device.argtypes = [vp, C.POINTER(GaeDesc)]
   _lib = lib
   return lib
 
@@ -480,6 +490,24 @@ class Context:
     byte of d_mask (device pointer of [n_envs] bytes; None: every env), enqueued on the context stream - no wait, no host
     copy.  The other rows of d_dst are not written."""
     self._check(self.lib.sag_copy_rows_device(self.h, d_mask, int(row_bytes), d_src, d_dst), 'sag_copy_rows_device')
+
+  def append_rows(self, d_mask, row_bytes, d_src, d_store, capacity, d_count, restart, d_slot):
+    """sag_append_rows_device: row i of d_src -> the next free slot of d_store ([capacity] rows) for the envs with a non-zero
+    byte of d_mask, d_slot[i] = that slot (-1: not set, or the store was full), d_count = slots claimed so far (one device
+    int32, zeroed first when restart), enqueued on the context stream - no wait, no host copy."""
+    self._check(self.lib.sag_append_rows_device(self.h, d_mask, int(row_bytes), d_src, d_store, int(capacity), d_count,
+                                                int(bool(restart)), d_slot), 'sag_append_rows_device')
+
+  def gae(self, T, pitch, d_reward, d_cost, d_ended, d_value, d_adv, d_ret, gamma, lam, d_cvalue=None, d_cadv=None, d_cret=None,
+          cost_gamma=None, cost_lam=None, d_slot=None, capacity=0, d_final_value=None, d_final_cvalue=None):
+    """sag_gae_device: advantages and returns over T stored steps of [T][pitch] arrays, for the reward channel and (d_cvalue
+    given) the cost channel, enqueued on the context stream.  Pointers are c_void_p, ints or None; cost_gamma / cost_lam
+    default to gamma / lam."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = GaeDesc(int(T), int(pitch), int(capacity), 0, float(gamma), float(lam), float(gamma if cost_gamma is None else cost_gamma),
+                float(lam if cost_lam is None else cost_lam), *[ptr(x) for x in (d_reward, d_cost, d_ended, d_value, d_cvalue, d_slot,
+                                                                                 d_final_value, d_final_cvalue, d_adv, d_ret, d_cadv, d_cret)])
+    self._check(self.lib.sag_gae_device(self.h, C.byref(d)), 'sag_gae_device')
 
   def fork_device(self, d_src, source=None, same_stream=False, flags=None):
     """sag_fork_device: env i takes the complete state of env d_src[i] of `source` (a Context on the same device; default:

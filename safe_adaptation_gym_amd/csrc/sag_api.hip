@@ -23,6 +23,7 @@
 #include "sag_rollout.hpp"
 #include "sag_fork.hpp"
 #include "sag_plan.hpp"
+#include "sag_buffer.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -1145,6 +1146,60 @@ int sag_plan_clear_device(sag_ctx* c, int32_t G, int32_t H, const uint8_t* d_mas
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const size_t total = (size_t)H * G * c->rb.nu;
   hipLaunchKernelGGL(k_plan_clear, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, H, G, c->rb.nu, d_mask, d_mean, d_sigma, sigma_init);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+// ---- rollout buffer (sag_buffer.hpp) ----
+int sag_append_rows_device(sag_ctx* c, const uint8_t* d_mask, int32_t row_bytes, const void* d_src, void* d_store, int32_t capacity,
+                           int32_t* d_count, int32_t restart, int32_t* d_slot) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d_mask || !d_src || !d_store || !d_count || !d_slot || d_src == d_store)
+    return fail(c, SAG_ERR_ARG, "sag_append_rows_device: d_mask, d_src, d_store, d_count and d_slot must be given, d_src and d_store two buffers");
+  if (row_bytes <= 0 || (row_bytes & 15)) return fail(c, SAG_ERR_ARG, "sag_append_rows_device: row_bytes %d is not a positive multiple of 16", row_bytes);
+  if (misaligned(d_src, 16) || misaligned(d_store, 16)) return fail(c, SAG_ERR_ARG, "sag_append_rows_device: d_src and d_store must be 16-byte aligned");
+  if (misaligned(d_count, 4) || misaligned(d_slot, 4)) return fail(c, SAG_ERR_ARG, "sag_append_rows_device: d_count and d_slot must be 4-byte aligned");
+  if (capacity < 1) return fail(c, SAG_ERR_ARG, "sag_append_rows_device: capacity = %d", capacity);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (restart) HIPCHK(c, hipMemsetAsync(d_count, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(k_append_rows, dim3((c->N + WAVE - 1) / WAVE), dim3(WAVE), 0, c->stream, c->N, d_mask, row_bytes / 16,
+                     reinterpret_cast<const float4*>(d_src), reinterpret_cast<float4*>(d_store), capacity, reinterpret_cast<int*>(d_count), d_slot);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+int sag_gae_device(sag_ctx* c, const sag_gae_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d) return fail(c, SAG_ERR_ARG, "sag_gae_device: desc is NULL");
+  if (d->T < 1 || d->pitch < c->N) return fail(c, SAG_ERR_ARG, "sag_gae_device: T = %d, pitch = %d (%d envs)", d->T, d->pitch, c->N);
+  if (c->N >= (1 << 28)) return fail(c, SAG_ERR_UNSUPPORTED, "sag_gae_device: %d envs (the kernel's lane offsets are 32-bit: fewer than 2^28)", c->N);
+  auto unit = [](float x) { return x >= 0.0f && x <= 1.0f; };   // (false for a NaN)
+  if (!unit(d->gamma) || !unit(d->lam) || !unit(d->cost_gamma) || !unit(d->cost_lam))
+    return fail(c, SAG_ERR_ARG, "sag_gae_device: gamma = %g, lam = %g, cost_gamma = %g, cost_lam = %g: each in [0, 1]", (double)d->gamma,
+                (double)d->lam, (double)d->cost_gamma, (double)d->cost_lam);
+  if (!d->d_reward || !d->d_cost || !d->d_ended || !d->d_value || !d->d_adv || !d->d_ret)
+    return fail(c, SAG_ERR_ARG, "sag_gae_device: d_reward, d_cost, d_ended, d_value, d_adv and d_ret must be given");
+  const bool cost = d->d_cvalue != nullptr;
+  if (cost != (d->d_cadv != nullptr) || cost != (d->d_cret != nullptr))
+    return fail(c, SAG_ERR_ARG, "sag_gae_device: d_cadv and d_cret go with d_cvalue - all three or none");
+  if (d->d_slot && d->capacity < 1) return fail(c, SAG_ERR_ARG, "sag_gae_device: d_slot with capacity = %d", d->capacity);
+  if (misaligned(d->d_reward, 8) || misaligned(d->d_value, 4) || misaligned(d->d_cvalue, 4) || misaligned(d->d_slot, 4) ||
+      misaligned(d->d_final_value, 4) || misaligned(d->d_final_cvalue, 4) || misaligned(d->d_adv, 4) || misaligned(d->d_ret, 4) ||
+      misaligned(d->d_cadv, 4) || misaligned(d->d_cret, 4))
+    return fail(c, SAG_ERR_ARG, "sag_gae_device: a misaligned buffer (d_reward 8 bytes; floats and ints 4)");
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  GaeArgs a;
+  a.N = c->N; a.T = d->T; a.pitch = d->pitch; a.capacity = d->capacity;
+  a.gamma = d->gamma; a.gl = d->gamma * d->lam; a.cgamma = d->cost_gamma; a.cgl = d->cost_gamma * d->cost_lam;
+  a.reward = d->d_reward; a.cost = d->d_cost; a.ended = d->d_ended; a.value = d->d_value; a.cvalue = d->d_cvalue;
+  a.slot = d->d_slot; a.final_value = d->d_final_value; a.final_cvalue = cost ? d->d_final_cvalue : nullptr;
+  a.adv = d->d_adv; a.ret = d->d_ret; a.cadv = d->d_cadv; a.cret = d->d_cret;
+  const bool slot = a.slot && (a.final_value || a.final_cvalue);   // (slots without final values change nothing: not loaded)
+  const dim3 grid((c->N + WAVE - 1) / WAVE), block(WAVE);
+  if (cost && slot) hipLaunchKernelGGL((k_gae<true, true>), grid, block, 0, c->stream, a);
+  else if (cost) hipLaunchKernelGGL((k_gae<true, false>), grid, block, 0, c->stream, a);
+  else if (slot) hipLaunchKernelGGL((k_gae<false, true>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_gae<false, false>), grid, block, 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }
