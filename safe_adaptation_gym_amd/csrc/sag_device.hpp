@@ -26,16 +26,23 @@ namespace sag {
 constexpr int WAVE = 64;
 
 // device int fields.  TSTATE is a plain [N] column (k_compact and the quiet kernel's busy test read
-// only it); the other four words of an env sit together as one int4 behind it.
-enum { DI_META = 0, DI_TSTATE = 1, DI_STEP = 2, DI_ENVID = 3, DI_FLAGS = 4, DI_COUNT = 5 };
+// only it); the other four words of an env sit together as one int4 behind it.  No step rewrites that int4: its second
+// word holds the bits of the pillar-size float (SAG_F_PILLAR_SIZE never changes), and the step counter (SAG_I_STEP) lives
+// in the float state instead, in group 1, which every step stores whole anyway (DF_STEP below).
+enum { DI_META = 0, DI_TSTATE = 1, DI_PSZ = 2, DI_ENVID = 3, DI_FLAGS = 4, DI_COUNT = 5 };
 // the FLAGS word: record flags in the low byte, the episode nonce (SAG_I_EPISODE) above it
 constexpr int FLAG_EPISODE_SHIFT = 8;
 // (the int4 block starts on a 16-byte boundary for any N: the TSTATE column is padded to a multiple of four words)
 __host__ __device__ constexpr size_t ipad(size_t N) { return (N + 3) & ~(size_t)3; }
 __host__ __device__ constexpr size_t icount(size_t N) { return ipad(N) + 4 * N; }   // words of the whole block
 __host__ __device__ constexpr size_t iaddr(int w, size_t N, size_t i) {
-  return w == DI_TSTATE ? i : ipad(N) + i * 4 + (w == DI_META ? 0 : (w == DI_STEP ? 1 : (w == DI_ENVID ? 2 : 3)));
+  return w == DI_TSTATE ? i : ipad(N) + i * 4 + (w == DI_META ? 0 : (w == DI_PSZ ? 1 : (w == DI_ENVID ? 2 : 3)));
 }
+// The two values that live in a slot of the other type - the counter's int32 bits in a float slot, the pillar size's float
+// bits in an int word - only ever travel through loads, stores and __int_as_float / __float_as_int.  The counter must never
+// pass through an arithmetic or min / max instruction AS A FLOAT: small ints are denormal bit patterns, and such an
+// instruction may flush or canonicalise them.
+__device__ inline float dev_pillar_size(const int32_t* I, size_t N, size_t i) { return __int_as_float(I[iaddr(DI_PSZ, N, i)]); }
 
 // ---- device layout of the float state ---------------------------------------------------------
 // Groups of four floats per env, group-major: float4 number g of env i is ((float4*)S)[g * N + i].
@@ -43,7 +50,7 @@ __host__ __device__ constexpr size_t iaddr(int w, size_t N, size_t i) {
 // plain field-major layout), and a GATHER - the busy kernel reading scattered envs - moves a quarter
 // of the cache lines per useful float.  The order inside the device record follows what the step
 // prologue reads together, not the order of the ABI record (k_install / k_extract translate):
-//   0 robot x y yaw vx | 4 vy w last0 pillar_size | 8 goal_x goal_y gear damp | 12 action_noise
+//   0 robot x y yaw vx | 4 vy w last0 STEP (int32 bits, DF_STEP) | 8 goal_x goal_y gear damp | 12 action_noise
 //   ctrl_scale0,1 vase_size | 16 pillars | 20..37 hazards, 38 hazard_size, 39 bound |
 //   40.. (x y) of the 11 free bodies (vases, then the task object), 62-63 unused | 64.. their yaw, 75 unused |
 //   76.. their velocities (vx vy w) | 112 buttons | 124 catch | 128 last1,2 | 130 keepouts | 136 rebuild pose |
@@ -53,6 +60,9 @@ __host__ __device__ constexpr size_t iaddr(int w, size_t N, size_t i) {
 constexpr int DEV_FLOATS = 192, DEV_GROUPS = DEV_FLOATS / 4;
 constexpr int DV_XY = 40, DV_YAW = 64, DV_VEL = 76, DG_HAZ = 5, DG_XY = DV_XY / 4, DG_YAW = DV_YAW / 4, DG_PILLARS = 4, DG_BUTTONS = 28;
 constexpr int XY_GROUPS = 6, YAW_GROUPS = 3;
+// Device float 7, the last of group 1, is no record float: it holds the bits of the step counter (see iaddr: loads, stores
+// and bit casts only).  The pillar size, the one record float without a device float (didx = DF_NONE), is an int word.
+constexpr int DF_STEP = 7, DF_NONE = -1;
 __host__ __device__ constexpr int didx(int k) {
   return k < 6 ? k
        : k < 9 ? 136 + (k - 6)
@@ -61,7 +71,7 @@ __host__ __device__ constexpr int didx(int k) {
        : k < 24 ? 140 + (k - 14)
        : k == 24 ? 38
        : k == 25 ? 15
-       : k == 26 ? 7
+       : k == 26 ? DF_NONE
        : k < 32 ? 130 + (k - 27)
        : k < 34 ? 8 + (k - 32)
        : k < 38 ? 124 + (k - 34)
@@ -85,10 +95,13 @@ static_assert(didx(SAG_F_BUTTONS) == 112 && didx(SAG_F_VASES + 6 * 3 + 4) == DV_
 static_assert(didx(SAG_F_VASES) == DV_XY && didx(SAG_F_VASES + 6 * 9 + 1) == DV_XY + 19 && didx(SAG_F_BOX) == DV_XY + 2 * SAG_MAX_VASES &&
               didx(SAG_F_VASES + 2) == DV_YAW && didx(SAG_F_VASES + 6 * 9 + 2) == DV_YAW + 9 && didx(SAG_F_BOX + 2) == DV_YAW + SAG_MAX_VASES &&
               DV_XY + 4 * XY_GROUPS == DV_YAW && DV_YAW + 4 * YAW_GROUPS == DV_VEL, "the (x, y) run and the yaw run of the free bodies");
-// every record float has a device float of its own, inside the device record
+// every record float but the pillar size has a device float of its own, inside the device record and not the counter's
 constexpr bool didx_is_a_layout() {
   bool used[DEV_FLOATS] = {};
+  used[DF_STEP] = true;
+  if (didx(SAG_F_PILLAR_SIZE) != DF_NONE) return false;
   for (int k = 0; k < SAG_REC_FLOATS; k++) {
+    if (k == SAG_F_PILLAR_SIZE) continue;
     const int d = didx(k);
     if (d < 0 || d >= DEV_FLOATS || used[d]) return false;
     used[d] = true;
@@ -97,8 +110,10 @@ constexpr bool didx_is_a_layout() {
 }
 static_assert(didx_is_a_layout(), "didx is injective over the record floats and stays below DEV_FLOATS");
 __host__ __device__ constexpr size_t saddr(int k, size_t N, size_t i) {
-  return ((size_t)(didx(k) >> 2) * N + i) * 4 + (didx(k) & 3);
+  return ((size_t)(didx(k) >> 2) * N + i) * 4 + (didx(k) & 3);   // (not for SAG_F_PILLAR_SIZE: dev_pillar_size)
 }
+__host__ __device__ constexpr size_t step_addr(size_t N, size_t i) { return ((size_t)(DF_STEP >> 2) * N + i) * 4 + (DF_STEP & 3); }
+__device__ inline int32_t dev_step(const float* S, size_t N, size_t i) { return __float_as_int(S[step_addr(N, i)]); }
 
 // ---- packing of the int record into two device words -----------------------
 __host__ __device__ inline uint32_t pack_meta(const int32_t* ri) {
@@ -139,7 +154,7 @@ struct StepArgs {
   uint8_t* kind;      // [N] kind of every busy env, for the next step's compaction
   int32_t* busy_total;  // the busy launch leaves its env count here
   float* S;          // [DEV_GROUPS][N] float4 (see didx)
-  int32_t* I;        // tstate [N], then (meta, step, envid, flags) [N] int4 (see iaddr)
+  int32_t* I;        // tstate [N], then (meta, pillar-size bits, envid, flags) [N] int4 (see iaddr)
   int32_t N;
   const float* actions;   // [N][nu]
   const float* noise;     // [N][nu] or nullptr
@@ -175,7 +190,8 @@ struct StepArgs {
 // words and tstate), contiguous per env = two cache lines.  The busy kernel reads compacted, scattered
 // envs: from the group-major state that is one cache line per group (~16 per env); the hot record is
 // written by whichever kernel classifies an env busy for the next step (~10 % of the envs) and by
-// k_hot_refresh after an install.
+// k_hot_refresh after an install.  Slots hold whole groups as they are in the state: the step counter is in slot 1 (the
+// copy of group 1), the pillar size in slot 14 (the copy of the int4).
 constexpr int HOT_GROUPS = 16, HOT_FLOATS = 4 * HOT_GROUPS;
 constexpr int DR_STRIDE = 20;  // qacc_lin 3, touch 8, comvel 4, cost_contacts, btn_mask, row overflow, pad
 
@@ -1074,16 +1090,16 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     tstate = (uint32_t)I[iaddr(DI_TSTATE, (size_t)N, (size_t)i)];
   }
   const uint32_t meta = (uint32_t)iw.x;
-  int step = iw.y;
   const uint32_t env_id = (uint32_t)iw.z;
   const float4 gA = GH(0, 0), gB = GH(1, 1), gC = GH(2, 2), gD = GH(3, 3);
+  int step = __float_as_int(gB.w);   // the counter rides in group 1 (DF_STEP), the pillar size in the int4 (DI_PSZ)
   BV R;
   R.x = gA.x; R.y = gA.y;
   float yaw = gA.z;
   R.vx = gA.w; R.vy = gB.x; R.w = gB.y;
   R.ax = R.ay = R.aw = 0; R.dyn = 1;
   const float gear = gC.z, damp = gC.w;
-  const float vsz = gD.w, psz = gB.w;
+  const float vsz = gD.w, psz = __int_as_float(iw.y);
   // car: wheel rates L, R; rear ball rate x, y, z (base axes); ball quaternion w, x, y, z
   float ext[9] = {0, 0, 0, 0, 0, 1, 0, 0, 0}, eacc[5] = {0, 0, 0, 0, 0};
   // (whole float4 groups: nine dword accesses at a 16-byte stride never cover a line, and the partial lines of the
@@ -1800,9 +1816,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
       const int d = dy.slot(k);
       if (d >= 0) { SD(fv) = POOL(d, 0); SD(fv + 1) = POOL(d, 1); SD(fv + 2) = POOL(d, 2); }
     }
-    step += 1;
-    // whole int4 (meta, step, envid, flags): a 4-byte store at a 16-byte stride would leave partial lines
-    reinterpret_cast<int4*>(I + ipad((size_t)N))[i] = make_int4(iw.x, step, iw.z, iw.w);
+    step += 1;   // (stored with group 1, behind the reward block; the int4 is not rewritten)
   }
   tstate = (tstate & ~(TS_AWAKE_BITS << TS_AWAKE_SHIFT)) | (awake & TS_AWAKE_BITS) << TS_AWAKE_SHIFT;
   // ---- classification for the NEXT step (QUIET / BUSY split): busy unless provably nothing can
@@ -2136,21 +2150,17 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     }
     if (live) {
       if (has_box) { SF(SAG_F_LAST + 1) = box_last1; SF(SAG_F_LAST + 2) = box_last2; }
-      if constexpr (DOGGO) {
-        SF(SAG_F_LAST) = last0;
-        SF(SAG_F_GOAL) = goalx; SF(SAG_F_GOAL + 1) = goaly;
-      }
+      if constexpr (DOGGO) { SF(SAG_F_GOAL) = goalx; SF(SAG_F_GOAL + 1) = goaly; }
     }
   }
-  if constexpr (!DOGGO) {
-    // group 1 (vy w last0 pillar_size) as a whole float4: full lines instead of scattered dwords.  Group 2 (goal gear
-    // damp) only where the goal moved: a resample, or CatchGoal's orbit.  A failed env (PhysicsError) keeps its old
-    // goal and `last`.
-    if (!p.observe_only && live) {
-      float4* __restrict__ W4 = reinterpret_cast<float4*>(S);
-      W4[(size_t)1 * N + i] = make_float4(R.vy, R.w, bad ? gB.z : last0, gB.w);
+  // group 1 (vy w last0 step) as a whole float4: full lines instead of scattered dwords, and the one store that carries the
+  // step counter (step + 1 here).  Doggo: vy and w are what k_doggo_physics stored, as loaded.  Group 2 (goal gear damp)
+  // only where the goal moved: a resample, or CatchGoal's orbit.  A failed env (PhysicsError) keeps its old goal and `last`.
+  if (!p.observe_only && live) {
+    float4* __restrict__ W4 = reinterpret_cast<float4*>(S);
+    W4[(size_t)1 * N + i] = make_float4(DOGGO ? gB.x : R.vy, DOGGO ? gB.y : R.w, bad ? gB.z : last0, __int_as_float(step));
+    if constexpr (!DOGGO)
       if (!bad && (need_goal || task == SAG_TASK_CATCH_GOAL)) W4[(size_t)2 * N + i] = make_float4(goalx, goaly, gC.z, gC.w);
-    }
   }
   if (!p.observe_only && live) I[iaddr(DI_TSTATE, (size_t)N, (size_t)i)] = (int32_t)tstate;
   if constexpr (MODE != MODE_ALL && !DOGGO) {
@@ -2159,7 +2169,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
     if (p.hot && busy_next && live && !p.observe_only) {
       float4* __restrict__ Hw = reinterpret_cast<float4*>(p.hot) + (size_t)i * HOT_GROUPS;
       Hw[0] = make_float4(R.x, R.y, yaw, R.vx);
-      Hw[1] = make_float4(R.vy, R.w, bad ? gB.z : last0, gB.w);
+      Hw[1] = make_float4(R.vy, R.w, bad ? gB.z : last0, __int_as_float(step));
       Hw[2] = make_float4(bad ? gC.x : goalx, bad ? gC.y : goaly, gC.z, gC.w);
       Hw[3] = gD;
       Hw[4] = make_float4(stx[0], sty[0], stx[1], sty[1]);
@@ -2174,7 +2184,7 @@ __device__ __forceinline__ void step_body(const StepArgs& p, float* lds, const i
         }
         Hw[5 + g] = make_float4(v[0], v[1], v[2], v[3]);
       }
-      Hw[14] = make_float4(__int_as_float(iw.x), __int_as_float(step), __int_as_float(iw.z), __int_as_float(iw.w | flags));
+      Hw[14] = make_float4(__int_as_float(iw.x), __int_as_float(iw.y), __int_as_float(iw.z), __int_as_float(iw.w | flags));
       Hw[15] = make_float4(__int_as_float((int)tstate), 0.f, 0.f, 0.f);
     }
   }
@@ -2627,7 +2637,11 @@ __global__ __launch_bounds__(256) void k_hot_refresh(const float* __restrict__ S
 // rec_f [n][SAG_REC_FLOATS], rec_i [n][SAG_REC_INTS] in device memory (AoS staging).
 // one record (rf, ri) -> env i
 __device__ inline void install_env(float* S, int32_t* I, int N, int i, const float* rf, const int32_t* ri, int init_task) {
-  for (int k = 0; k < SAG_REC_FLOATS; k++) S[saddr(k, (size_t)N, (size_t)i)] = rf[k];
+  for (int k = 0; k < SAG_REC_FLOATS; k++)
+    if (k != SAG_F_PILLAR_SIZE) S[saddr(k, (size_t)N, (size_t)i)] = rf[k];
+  // the pillar size is an int word, the step counter a float of group 1 (iaddr, DF_STEP): bits only, either way
+  I[iaddr(DI_PSZ, (size_t)N, (size_t)i)] = __float_as_int(rf[SAG_F_PILLAR_SIZE]);
+  S[step_addr((size_t)N, (size_t)i)] = __int_as_float(ri[SAG_I_STEP]);
   // derived word: which free bodies are awake = have a non-zero velocity component (SPECIFICATION, oracle world_forward
   // "sleeping bodies": a resting body takes part in a forward evaluation only once something active touches it), or are
   // flagged in SAG_I_AWAKE.  An install of a NEW world (sag_set_layout) flags the bodies whose bounding circle overlaps
@@ -2671,7 +2685,6 @@ __device__ inline void install_env(float* S, int32_t* I, int N, int i, const flo
   I[iaddr(DI_META, (size_t)N, (size_t)i)] = (int32_t)pack_meta(ri);
   // the first step after an install runs in BUSY mode (nothing has been classified yet)
   I[iaddr(DI_TSTATE, (size_t)N, (size_t)i)] = (int32_t)(pack_tstate(ri) | awake << TS_AWAKE_SHIFT | TS_BUSY_BIT | TS_BUSY_BIT << 1);
-  I[iaddr(DI_STEP, (size_t)N, (size_t)i)] = ri[SAG_I_STEP];
   I[iaddr(DI_ENVID, (size_t)N, (size_t)i)] = ri[SAG_I_ENV_ID];
   I[iaddr(DI_FLAGS, (size_t)N, (size_t)i)] = (ri[SAG_I_FLAGS] & 0xff) | (int32_t)((uint32_t)ri[SAG_I_EPISODE] << FLAG_EPISODE_SHIFT);
   if (init_task) {
@@ -2703,11 +2716,12 @@ __global__ void k_install(float* S, int32_t* I, int N, const int32_t* env_ids, i
 
 // env i -> one record (rf, ri)
 __device__ inline void extract_env(const float* S, const int32_t* I, int N, int i, float* rf, int32_t* ri) {
-  for (int k = 0; k < SAG_REC_FLOATS; k++) rf[k] = S[saddr(k, (size_t)N, (size_t)i)];
+  for (int k = 0; k < SAG_REC_FLOATS; k++)
+    rf[k] = k != SAG_F_PILLAR_SIZE ? S[saddr(k, (size_t)N, (size_t)i)] : dev_pillar_size(I, (size_t)N, (size_t)i);
   for (int k = 0; k < SAG_REC_INTS; k++) ri[k] = 0;
   unpack_meta((uint32_t)I[iaddr(DI_META, (size_t)N, (size_t)i)], ri);
   unpack_tstate((uint32_t)I[iaddr(DI_TSTATE, (size_t)N, (size_t)i)], ri);
-  ri[SAG_I_STEP] = I[iaddr(DI_STEP, (size_t)N, (size_t)i)];
+  ri[SAG_I_STEP] = dev_step(S, (size_t)N, (size_t)i);
   ri[SAG_I_ENV_ID] = I[iaddr(DI_ENVID, (size_t)N, (size_t)i)];
   const uint32_t fw = (uint32_t)I[iaddr(DI_FLAGS, (size_t)N, (size_t)i)];
   ri[SAG_I_FLAGS] = (int32_t)(fw & 0xffu);

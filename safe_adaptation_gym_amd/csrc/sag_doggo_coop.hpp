@@ -1039,7 +1039,7 @@ __global__ __launch_bounds__(32 * DC_EPW) void k_doggo_physics(StepArgs p, doubl
   const int box_kind = meta >> 17 & 3;
   W.has_box = box_kind != SAG_BOX_NONE;
   W.haul = W.task == SAG_TASK_HAUL_BOX;
-  W.vsz = S[saddr(SAG_F_VASE_SIZE, N, i)]; W.psz = S[saddr(SAG_F_PILLAR_SIZE, N, i)];
+  W.vsz = S[saddr(SAG_F_VASE_SIZE, N, i)]; W.psz = dev_pillar_size(p.I, N, i);
   const float h = p.h;
   {
     const float tc = fmaxf(0.02f, 2.0f * h);
@@ -1098,7 +1098,7 @@ __global__ __launch_bounds__(32 * DC_EPW) void k_doggo_physics(StepArgs p, doubl
       float z;
       if (p.noise) z = p.noise[i * 12 + u];
       else {
-        const uint32_t env_id = (uint32_t)p.I[iaddr(DI_ENVID, N, i)], step = (uint32_t)p.I[iaddr(DI_STEP, N, i)];
+        const uint32_t env_id = (uint32_t)p.I[iaddr(DI_ENVID, N, i)], step = (uint32_t)dev_step(S, N, i);
         const uint32_t ep4 = ((uint32_t)p.I[iaddr(DI_FLAGS, N, i)] >> FLAG_EPISODE_SHIFT) << 2;
         uint32_t cc[4] = {env_id, step, (uint32_t)(u >> 1), ep4 | 1u};
         philox4x32_10(cc, p.key0, p.key1);

@@ -253,7 +253,7 @@ __device__ __forceinline__ RCounts r_build_scene(const RenderArgs& a, const size
   for (int k = 0; k < nV; k++)
     r_obj(ob, n, 0, F(SAG_F_VASES + 6 * k), F(SAG_F_VASES + 6 * k + 1), vs - 4e-5, vs, vs, vs, F(SAG_F_VASES + 6 * k + 2), 0, 1, 1, 1.0);
   for (int k = 0; k < nP; k++)
-    r_obj(ob, n, 1, F(SAG_F_PILLARS + 2 * k), F(SAG_F_PILLARS + 2 * k + 1), 0.5, F(SAG_F_PILLAR_SIZE), 0, 0.5, 0.0, .5, .5, 1, 1.0);
+    r_obj(ob, n, 1, F(SAG_F_PILLARS + 2 * k), F(SAG_F_PILLARS + 2 * k + 1), 0.5, (double)dev_pillar_size(a.I, (size_t)N, i), 0, 0.5, 0.0, .5, .5, 1, 1.0);
   const bool goal_body = !(task == SAG_TASK_PRESS_BUTTONS || task == SAG_TASK_PRESS_BUTTONS_SCARCE || task == SAG_TASK_COLLECT);
   if (goal_body)
     r_obj(ob, n, 1, F(SAG_F_GOAL), F(SAG_F_GOAL + 1), GOAL_Z, GOAL_SIZE, 0, GOAL_SIZE / 2, 0.0, 0, 1, 0,
