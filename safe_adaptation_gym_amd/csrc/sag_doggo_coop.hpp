@@ -1241,11 +1241,12 @@ __global__ __launch_bounds__(32 * DC_EPW) void k_doggo_physics(StepArgs p, doubl
     }
     dc_contacts_finish(hf, u, r0, (nrows - r0) / 3);
     if (W.has_box) {
-      if (W.haul && nrows >= DC_ROWS && u == 0) E.flag |= 2;
-      if (W.haul && nrows < DC_ROWS) {   // haul_box.py:21-29: tendon base site <-> box site (z .2), range [0, .75]
+      if (W.haul) {   // haul_box.py:21-29: tendon base site <-> box site (z .2), range [0, .75]
         const double dx = (double)E.wfb[BOX_ID][0] - E.pos[0], dy = (double)E.wfb[BOX_ID][1] - E.pos[1], dz = 0.2 - E.pos[2];
         const double d2 = dx * dx + dy * dy, Lt = sqrt(d2 + dz * dz), viol = Lt - 0.75;
-        if (viol > 0 && d2 >= 1e-18) {
+        if (viol > 0 && d2 >= 1e-18 && nrows >= DC_ROWS) {
+          if (u == 0) E.flag |= 2;   // the taut tether's row did not fit (a slack tether has no row to drop)
+        } else if (viol > 0 && d2 >= 1e-18) {
           if (u == 0) {
             const double j[3] = {dx / Lt, dy / Lt, dz / Lt};
             dc_jac(hf, nrows, 0, E.pos, j);

@@ -97,6 +97,21 @@ def lockstep_state_tol(robot, task, ncol):
   return tol64, tol32
 
 
+def doggo_state_tol(ncol):
+  """The Doggo lockstep's per-column state tolerance (abs; the same value again relative) after one step from identical
+  fp32 state: robot qpos within 2e-5, qvel within 2e-3, free bodies within the planar STATE_TOL (spin 2e-4; the task
+  object's 5e-3)."""
+  E = 144
+  pos_f = [0, 1, 2, E] + list(range(E + 1, E + 5)) + list(range(E + 9, E + 22))
+  tol = np.full(ncol, 2e-3)
+  tol[pos_f] = 2e-5
+  for k in range(10):
+    tol[81 + 6 * k:81 + 6 * k + 6] = STATE_TOL
+    tol[81 + 6 * k + 5] = 2e-4
+  tol[41:47] = STATE_TOL; tol[46] = 5e-3
+  return tol
+
+
 def rows_outside(d_rf, o_rf, tol):
   """Rows of d_rf with a column outside tol (abs + rel) of o_rf."""
   return (np.abs(d_rf - o_rf) > tol + tol * np.abs(o_rf)).any(1)

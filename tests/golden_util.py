@@ -11,7 +11,7 @@ from oracle_lib import (F_ACTION_NOISE, F_BOX, F_BUTTONS, F_CATCH, F_CTRL_SCALE,
                         F_PILLAR_SIZE, F_PILLARS, F_ROBOT, F_ROBOT0, F_VASE_SIZE, F_VASES,
                         I_ACTIVE_MASK, I_BOX_KIND, I_BTN_STATE, I_BTN_TIMER, I_CATCH_TIMER,
                         I_ENV_ID, I_GOAL_BUTTON, I_NB, I_NH, I_NP, I_NV, I_STEP, I_TASK,
-                        REC_FLOATS, REC_INTS)
+                        F_ROBOT_EXT, REC_FLOATS, REC_INTS)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
@@ -155,6 +155,17 @@ def base_record(task, names, keepouts, env_id=0, robot='point'):
   rf[F_CATCH + 2], rf[F_CATCH + 3] = 1.0, 0.2  # catch_goal.py:15-16
   if robot != 'doggo':
     rf[144 + 5] = 1.0  # car rear-ball quaternion w (ignored by point)
+  return rf, ri
+
+
+def doggo_record(x=0.0, y=0.0, yaw=0.0, z=0.22, task='go_to_goal', names=('robot', 'goal')):
+  """A Doggo record at rest: base at (x, y, z) turned by yaw, joints 0, the goal out of the way."""
+  rf, ri = base_record(task, list(names), {'robot': 0.4})
+  rf[F_ROBOT:F_ROBOT + 3] = [x, y, yaw]
+  rf[F_ROBOT_EXT:F_ROBOT_EXT + 40] = 0     # (base_record presets the car's ball quaternion)
+  rf[F_ROBOT_EXT] = z
+  rf[F_ROBOT_EXT + 1:F_ROBOT_EXT + 5] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
+  rf[F_GOAL:F_GOAL + 2] = [5.0, 5.0]
   return rf, ri
 
 

@@ -22,6 +22,15 @@ F_BOUND = 141
  I_BTN_TIMER, I_CATCH_TIMER, I_ACTIVE_MASK, I_STEP, I_ENV_ID, I_FLAGS, I_EPISODE, I_AWAKE) = range(16)
 
 
+def decode_contact_key(key):
+  """(kind, floor point | (object, object geom, contact, robot geom)) of a Doggo contact row key (sag_oracle_doggo.inc)."""
+  key = int(key)
+  if key < 0x10000:
+    return 'floor', (key - 0x1000) // 4
+  q = (key - 0x10000) // 4
+  return 'object', (q // 2048, q // 256 % 8, q // 32 % 8, q % 32)
+
+
 def build(force=False):
   out = os.path.join(ORACLE_DIR, '_build', 'libsag_oracle.so')
   src = os.path.join(ORACLE_DIR, 'sag_oracle.c')

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
-from golden_util import base_record
+from golden_util import base_record, doggo_record  # noqa: F401 (doggo_record: other test modules take it from here)
 
 DOGGO = 2
 DT = 0.012
@@ -16,16 +16,6 @@ EXT = ol.F_ROBOT_EXT
 @pytest.fixture(scope='module')
 def oracle():
   return ol.Oracle()
-
-
-def doggo_record(x=0.0, y=0.0, yaw=0.0, z=0.22, task='go_to_goal', names=('robot', 'goal')):
-  rf, ri = base_record(task, list(names), {'robot': 0.4})
-  rf[ol.F_ROBOT:ol.F_ROBOT + 3] = [x, y, yaw]
-  rf[EXT:EXT + 40] = 0     # (base_record presets the car's ball quaternion)
-  rf[EXT] = z
-  rf[EXT + 1:EXT + 5] = [np.cos(yaw / 2), 0, 0, np.sin(yaw / 2)]
-  rf[ol.F_GOAL:ol.F_GOAL + 2] = [5.0, 5.0]
-  return rf, ri
 
 
 def capsule_mass(a, b, r=0.032, dens=5.0):
@@ -320,13 +310,7 @@ print(repr(float(o.doggo_debug(o.env(rf, ri))[0][0, 0])))
 
 
 # ---- collision geometry (round 4): the XML's capsules and cylinders, not spheres ----------------------------------
-def _decode(key):
-  """(kind, floor point | (object, object geom, contact, robot geom)) of a contact row key (sag_oracle_doggo.inc)."""
-  key = int(key)
-  if key < 0x10000:
-    return 'floor', (key - 0x1000) // 4
-  q = (key - 0x10000) // 4
-  return 'object', (q // 2048, q // 256 % 8, q // 32 % 8, q % 32)
+_decode = ol.decode_contact_key
 
 
 VASE0, PILLAR0 = 2 + 6, 0   # object numbering of the keys: pillars 0.., buttons 2.., vases 8.., task object 18

@@ -93,4 +93,4 @@ if len(res) == 2:
   doc['src_sha16'] = sha
   json.dump(doc, open(path, 'w'), indent=1)
   print(json.dumps(entry, indent=1))
-  print('merged into', path, 'for sources', sha)
+  print('merged into', os.path.relpath(path, root), 'for sources', sha)
