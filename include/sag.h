@@ -545,6 +545,56 @@ typedef struct sag_gae_desc {
 } sag_gae_desc;
 int sag_gae_device(sag_ctx* ctx, const sag_gae_desc* desc);
 
+/* ---- a Gaussian actor-critic MLP on the context stream (throughput mode) --------------------------
+ * sag_policy_forward_device: one fused forward of a two-hidden-layer MLP with a shared trunk and three heads,
+ *   obs [n_rows][obs_dim] -> hidden -> hidden -> nu + 2 outputs = action mean (nu), reward value, cost value,
+ * with obs_dim and nu the context's robot's.  One launch reads each observation row once and writes only the outputs; enqueued
+ * on the context stream, it returns without waiting, copies nothing to the host, records no timing events and needs no layout.
+ * What with the rollout buffer above closes the model-free loop on the device: the policy writes actions[t], logp[t], value[t]
+ * and cost_value[t] from obs[t], the step reads actions[t].
+ *
+ * d_params: contiguous fp32 in natural (row-major) layout, H = hidden:
+ *   W1[obs_dim][H]  b1[H]  W2[H][H]  b2[H]  W3[H][nu + 2]  b3[nu + 2]  std[nu]
+ * d_obs: n_rows rows of obs_pitch >= obs_dim floats (obs_pitch a multiple of 4, d_obs 16-byte aligned); rows at or beyond
+ * n_rows and the pad columns are not read.  n_rows is arbitrary (a final-observation store is not n_envs rows).
+ * Outputs, any of which may be NULL: d_actions [n_rows][nu], d_logp, d_value, d_cvalue [n_rows]; rows at or beyond n_rows are
+ * not written.
+ *
+ * The defined arithmetic.  Every unit j of every layer, in fp32:
+ *   acc = bias[j];   for k = 0 ... K - 1 in ascending order: acc = fmaf(x[k], W[k][j], acc);   y[j] = act(acc)
+ * (one rounding per product - the fp32-input matrix instruction computes exactly this chain); the head has no activation.
+ *   SAG_POLICY_RELU: act(x) = x > 0 ? x : 0
+ *   SAG_POLICY_TANH: act(x) = 1 - 2 * rcp(exp2(c * x) + 1), c = 2 log2(e) rounded to fp32, with the hardware exp2 and
+ *                    reciprocal (1 ulp-class) and every operation rounded on its own
+ * Sampling: a[u] = mean[u] + std[u] * z[u], the product and the sum rounded separately, written UNCLAMPED (the step clips; a
+ * learner needs the raw sample).  z[u] is a standard normal of the counter-based generator under the context key (sag_set_seed)
+ * on stream 5: the Philox4x32-10 block of the counter
+ *   word 0 = env_id0 (sag_set_tasks; 0 without tasks) + row0 + row    word 1 = draw    word 2 = u / 4    word 3 = 0x14000000
+ * gives u % 4 = 0, 1 the two normals (cos, sin) of the Box-Muller transform of its words 0, 1 and u % 4 = 2, 3 those of its
+ * words 2, 3, as sag_plan_sample_device maps them.  Word 3 is stream 5 placed above the 26 bits of streams 0 - 3.
+ *   logp = -(0.5f * sum_u z[u]^2) - logp_const, the sum in ascending u in fp32, each square and each sum rounded;
+ *   logp_const = sum_u log(std[u]) + nu * 0.5 * log(2 pi), rounded once by the caller.
+ * With SAG_POLICY_MEAN in flags, or with d_actions == NULL (the value-only evaluation), nothing is sampled: z = 0, the actions
+ * are the mean exactly and logp = -logp_const.
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc, d_params or d_obs; d_obs not 16-byte aligned, d_params or an output not
+ * 4-byte aligned; hidden not a multiple of 32 in 32 ... 256; an unknown activation or flag bit; obs_pitch < obs_dim or not a
+ * multiple of 4; n_rows < 1; a logp_const that is not finite. */
+enum sag_policy_activation { SAG_POLICY_RELU = 0, SAG_POLICY_TANH = 1 };
+enum sag_policy_flags { SAG_POLICY_MEAN = 1 };
+typedef struct sag_policy_desc {
+  int32_t n_rows, hidden, activation, flags;
+  int32_t obs_pitch, reserved;
+  uint32_t draw, row0;
+  float logp_const;
+  const float* d_params;
+  const float* d_obs;
+  float* d_actions;
+  float* d_logp;
+  float* d_value;
+  float* d_cvalue;
+} sag_policy_desc;
+int sag_policy_forward_device(sag_ctx* ctx, const sag_policy_desc* desc);
+
 /* ---- fork on the device (throughput mode) -------------------------------------------------------
  * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`
  * itself (a fork inside a batch) or another one, of any n_envs (a few real envs feeding many planner envs; a second context

@@ -14,6 +14,9 @@ def __getattr__(name):
   if name == 'RolloutBuffer':   # sag.RolloutBuffer(env, steps): time-major storage written in place, final rows, GAE (rollout_buffer.py)
     from safe_adaptation_gym_amd.rollout_buffer import RolloutBuffer
     return RolloutBuffer
+  if name == 'MLPPolicy':   # sag.MLPPolicy(env, hidden): a Gaussian actor-critic MLP whose forward runs on the device (policy.py)
+    from safe_adaptation_gym_amd.policy import MLPPolicy
+    return MLPPolicy
   raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 

@@ -36,7 +36,8 @@ EXPORTS = [
     'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
     'sag_episode_clear', 'sag_copy_rows_device', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
-    'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device'
+    'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device',
+    'sag_policy_forward_device'
 ]
 
 
@@ -66,6 +67,16 @@ class GaeDesc(C.Structure):
           (k, C.c_void_p) for k in ('d_reward', 'd_cost', 'd_ended', 'd_value', 'd_cvalue', 'd_slot', 'd_final_value',
                                     'd_final_cvalue', 'd_adv', 'd_ret', 'd_cadv', 'd_cret')]
 
+
+class PolicyDesc(C.Structure):
+  """sag_policy_desc (include/sag.h)."""
+  _fields_ = [(k, C.c_int32) for k in ('n_rows', 'hidden', 'activation', 'flags', 'obs_pitch', 'reserved')] + [
+      ('draw', C.c_uint32), ('row0', C.c_uint32), ('logp_const', C.c_float)] + [
+          (k, C.c_void_p) for k in ('d_params', 'd_obs', 'd_actions', 'd_logp', 'd_value', 'd_cvalue')]
+
+
+POLICY_RELU, POLICY_TANH = 0, 1   # enum sag_policy_activation
+POLICY_MEAN = 1                   # enum sag_policy_flags
 
 _lib = None
 
@@ -138,6 +149,7 @@ def load():
   lib.sag_plan_clear_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_float]
   lib.sag_append_rows_device.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp]
   lib.sag_gae_device.argtypes = [vp, C.POINTER(GaeDesc)]
+  lib.sag_policy_forward_device.argtypes = [vp, C.POINTER(PolicyDesc)]
   _lib = lib
   return lib
 
@@ -508,6 +520,17 @@ class Context:
                 float(lam if cost_lam is None else cost_lam), *[ptr(x) for x in (d_reward, d_cost, d_ended, d_value, d_cvalue, d_slot,
                                                                                  d_final_value, d_final_cvalue, d_adv, d_ret, d_cadv, d_cret)])
     self._check(self.lib.sag_gae_device(self.h, C.byref(d)), 'sag_gae_device')
+
+  def policy_forward(self, n_rows, hidden, d_params, d_obs, logp_const=0.0, d_actions=None, d_logp=None, d_value=None, d_cvalue=None,
+                     activation=POLICY_RELU, flags=0, draw=0, row0=0, obs_pitch=None):
+    """sag_policy_forward_device: the fused actor-critic forward of n_rows observation rows (obs_pitch floats apart; default
+    obs_dim) under the parameters at d_params (the header has their layout and the arithmetic), enqueued on the context stream
+    - no wait, no host copy.  Pointers are c_void_p, ints or None; an output that is None is not written."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = PolicyDesc(int(n_rows), int(hidden), int(activation), int(flags), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), 0,
+                   int(draw) & 0xffffffff, int(row0) & 0xffffffff, float(logp_const),
+                   *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp, d_value, d_cvalue)])
+    self._check(self.lib.sag_policy_forward_device(self.h, C.byref(d)), 'sag_policy_forward_device')
 
   def fork_device(self, d_src, source=None, same_stream=False, flags=None):
     """sag_fork_device: env i takes the complete state of env d_src[i] of `source` (a Context on the same device; default:

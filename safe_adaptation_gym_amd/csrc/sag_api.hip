@@ -24,6 +24,7 @@
 #include "sag_fork.hpp"
 #include "sag_plan.hpp"
 #include "sag_buffer.hpp"
+#include "sag_policy.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -1200,6 +1201,49 @@ int sag_gae_device(sag_ctx* c, const sag_gae_desc* d) {
   else if (cost) hipLaunchKernelGGL((k_gae<true, false>), grid, block, 0, c->stream, a);
   else if (slot) hipLaunchKernelGGL((k_gae<false, true>), grid, block, 0, c->stream, a);
   else hipLaunchKernelGGL((k_gae<false, false>), grid, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+// ---- actor-critic MLP (sag_policy.hpp) ----
+int sag_policy_forward_device(sag_ctx* c, const sag_policy_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: desc is NULL");
+  if (!d->d_params || !d->d_obs) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: d_params and d_obs must be given");
+  if (misaligned(d->d_obs, 16) || misaligned(d->d_params, 4) || misaligned(d->d_actions, 4) || misaligned(d->d_logp, 4) ||
+      misaligned(d->d_value, 4) || misaligned(d->d_cvalue, 4))
+    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: a misaligned buffer (d_obs 16 bytes; parameters and outputs 4)");
+  if (d->hidden < 32 || d->hidden > 32 * POLICY_MAX_TILES || (d->hidden & 31))
+    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: hidden = %d is not a multiple of 32 in 32 ... %d", d->hidden, 32 * POLICY_MAX_TILES);
+  if (d->activation != SAG_POLICY_RELU && d->activation != SAG_POLICY_TANH)
+    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: activation = %d", d->activation);
+  if (d->flags & ~SAG_POLICY_MEAN) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: unknown flag bits 0x%x", d->flags & ~SAG_POLICY_MEAN);
+  if (d->obs_pitch < c->rb.obs_dim || (d->obs_pitch & 3))
+    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: obs_pitch = %d (rows of %d floats, a multiple of 4)", d->obs_pitch, c->rb.obs_dim);
+  if (d->n_rows < 1) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: n_rows = %d", d->n_rows);
+  if (!std::isfinite(d->logp_const)) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: logp_const is not finite");
+  if (c->rb.obs_dim > POLICY_MAX_OBS || (c->rb.obs_dim & 3) || c->rb.nu + 2 > 16)
+    return fail(c, SAG_ERR_UNSUPPORTED, "sag_policy_forward_device: obs_dim = %d, nu = %d", c->rb.obs_dim, c->rb.nu);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  PolicyArgs a;
+  a.n_rows = d->n_rows; a.obs_dim = c->rb.obs_dim; a.nu = c->rb.nu; a.activation = d->activation;
+  a.mean_only = (d->flags & SAG_POLICY_MEAN) != 0; a.obs_pitch = d->obs_pitch; a.lds_pitch = policy_lds_pitch(c->rb.obs_dim);
+  const size_t lds = (size_t)POLICY_ROWS * a.lds_pitch * sizeof(float);
+  a.id0 = (uint32_t)c->env_id0 + d->row0; a.draw = d->draw;
+  a.k0 = (uint32_t)(c->cfg.seed & 0xffffffffu); a.k1 = (uint32_t)(c->cfg.seed >> 32);
+  a.logp_const = d->logp_const; a.params = d->d_params; a.obs = d->d_obs;
+  a.actions = d->d_actions; a.logp = d->d_logp; a.value = d->d_value; a.cvalue = d->d_cvalue;
+  const dim3 grid((unsigned)(((size_t)d->n_rows + POLICY_ROWS - 1) / POLICY_ROWS)), block(WAVE);
+  switch (d->hidden / 32) {
+    case 1: hipLaunchKernelGGL((k_policy_forward<1>), grid, block, lds, c->stream, a); break;
+    case 2: hipLaunchKernelGGL((k_policy_forward<2>), grid, block, lds, c->stream, a); break;
+    case 3: hipLaunchKernelGGL((k_policy_forward<3>), grid, block, lds, c->stream, a); break;
+    case 4: hipLaunchKernelGGL((k_policy_forward<4>), grid, block, lds, c->stream, a); break;
+    case 5: hipLaunchKernelGGL((k_policy_forward<5>), grid, block, lds, c->stream, a); break;
+    case 6: hipLaunchKernelGGL((k_policy_forward<6>), grid, block, lds, c->stream, a); break;
+    case 7: hipLaunchKernelGGL((k_policy_forward<7>), grid, block, lds, c->stream, a); break;
+    default: hipLaunchKernelGGL((k_policy_forward<8>), grid, block, lds, c->stream, a); break;
+  }
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }

@@ -1,0 +1,183 @@
+"""MLPPolicy: a Gaussian actor-critic MLP whose forward runs on the env's context stream (sag_policy_forward_device).
+
+With a RolloutBuffer it closes the model-free loop on the device - observe, policy and critics, step, track, append, reset and
+GAE are all enqueued on one stream, and nothing goes through the host between them:
+
+  buf.collect(pi)
+  pi.evaluate(buf)
+  buf.advantages(buf.value, buf.cost_value, buf.final_value, buf.final_cost_value)
+
+The network is obs -> hidden -> hidden -> nu + 2 outputs (action mean, reward value, cost value) with a state-independent
+standard deviation; include/sag.h defines its arithmetic.  NumPy only; no torch."""
+import numpy as np
+
+from safe_adaptation_gym_amd import _native as nat
+
+ACTIVATIONS = {'relu': nat.POLICY_RELU, 'tanh': nat.POLICY_TANH}
+KEYS = ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'std')
+
+
+class MLPPolicy:
+  """pi = MLPPolicy(env, hidden=64, activation='relu', seed=0, log_std=-0.5)
+
+  env: a BatchedSafeAdaptationGym in one context with vector observations; ValueError otherwise.
+  hidden: a multiple of 32 from 32 to 256.  Weights and biases are uniform in +-1 / sqrt(fan_in) from
+  np.random.RandomState(seed); std = exp(log_std).
+
+  params: {'W1' [obs_dim, hidden], 'b1', 'W2' [hidden, hidden], 'b2', 'W3' [hidden, nu + 2], 'b3', 'std' [nu]} - DeviceArray
+  views of ONE device buffer in the ABI's layout, which a learner may overwrite in place on the context's stream (after writing
+  'std' that way, call refresh() - the log-probability's constant is formed on the host).  set_params() / get_params() go
+  through the host.
+
+  Every method but set_params / get_params / refresh / evaluate only enqueues work: no wait, no host copy."""
+
+  def __init__(self, env, hidden=64, activation='relu', seed=0, log_std=-0.5):
+    from safe_adaptation_gym_amd.envs import BatchedSafeAdaptationGym
+    if not isinstance(env, BatchedSafeAdaptationGym):
+      raise ValueError('MLPPolicy: env must be a BatchedSafeAdaptationGym')
+    if env._rgb_observation:
+      raise ValueError('MLPPolicy: rgb_observation is not supported - the network reads vector observations')
+    if len(env._ctx) != 1:
+      raise ValueError(f'MLPPolicy: the env is sharded over {len(env._ctx)} contexts; one policy serves one context')
+    H = int(hidden)
+    if H != hidden or H < 32 or H > 256 or H % 32:
+      raise ValueError(f'MLPPolicy: hidden={hidden} is not a multiple of 32 from 32 to 256')
+    if activation not in ACTIVATIONS:
+      raise ValueError(f'MLPPolicy: activation={activation!r}: one of {sorted(ACTIVATIONS)}')
+    if not np.isfinite(log_std):
+      raise ValueError(f'MLPPolicy: log_std={log_std}')
+    self.env, self.hidden, self.activation = env, H, activation
+    self.obs_dim, self.nu = od, nu = env.robot.obs_dim, env.robot.nu
+    self._ctx = c = env._ctx[0]
+    self.draw = 0   # counter word 1 of the next sampled forward
+    self.shapes = {'W1': (od, H), 'b1': (H,), 'W2': (H, H), 'b2': (H,), 'W3': (H, nu + 2), 'b3': (nu + 2,), 'std': (nu,)}
+    self.n_params = sum(int(np.prod(s)) for s in self.shapes.values())
+    self._buf = c.dev_alloc(self.n_params * 4)
+    self.params, off = {}, 0
+    for k in KEYS:
+      self.params[k] = nat.DeviceArray(c, self._buf.value + 4 * off, self.shapes[k], np.float32)
+      off += int(np.prod(self.shapes[k]))
+    rng = np.random.RandomState(seed)
+    init = {}
+    for k in KEYS[:-1]:
+      bound = 1.0 / np.sqrt(self.shapes['W' + k[1]][0])   # a bias takes its layer's fan-in
+      init[k] = rng.uniform(-bound, bound, self.shapes[k]).astype(np.float32)
+    init['std'] = np.full(nu, np.exp(log_std), np.float32)
+    self.set_params(init)
+
+  # -- parameters ------------------------------------------------------------------------------------------------------
+  def set_params(self, params):
+    """Uploads a dict of NumPy arrays (every key of `params`, the shapes of `shapes`)."""
+    if set(params) != set(KEYS):
+      raise ValueError(f'MLPPolicy.set_params: the keys are {list(KEYS)}, not {sorted(params)}')
+    flat = []
+    for k in KEYS:
+      a = np.asarray(params[k], np.float32)
+      if a.shape != self.shapes[k]:
+        raise ValueError(f'MLPPolicy.set_params: {k} of shape {a.shape}, not {self.shapes[k]}')
+      flat.append(a.reshape(-1))
+    std = flat[-1]
+    if not (np.isfinite(std).all() and (std > 0).all()):
+      raise ValueError('MLPPolicy.set_params: std must be positive and finite')
+    self._ctx.dev_upload(self._buf, np.concatenate(flat))
+    self._set_const(std)
+
+  def get_params(self):
+    """Downloads the parameters -> dict of NumPy arrays.  Joins the stream."""
+    self._ctx.wait()
+    flat = self._ctx.dev_download(self._buf, (self.n_params,), np.float32)
+    out, off = {}, 0
+    for k in KEYS:
+      n = int(np.prod(self.shapes[k]))
+      out[k] = flat[off:off + n].reshape(self.shapes[k]).copy()
+      off += n
+    return out
+
+  def _set_const(self, std):
+    std = np.asarray(std, np.float64)
+    self.logp_const = float(np.float32(np.log(std).sum() + len(std) * 0.5 * np.log(2 * np.pi)))
+
+  def refresh(self):
+    """Forms the log-probability's constant again from the 'std' on the device (after a learner wrote it in place).  Joins
+    the stream."""
+    self._ctx.wait()
+    self._set_const(self.params['std'].numpy())
+
+  # -- the forward -------------------------------------------------------------------------------------------------------
+  def _rows(self, obs):
+    """(pointer, rows, pitch in floats) of a device view [rows, obs_dim] float32 whose rows are contiguous."""
+    if isinstance(obs, nat.DeviceArray):
+      typestr, shape, strides, ptr = obs.dtype.str, obs.shape, obs.strides, obs.ptr
+    else:
+      cai = getattr(obs, '__cuda_array_interface__', None)
+      if cai is None:
+        raise TypeError(f'MLPPolicy: {type(obs).__name__} is not a device array')
+      typestr, shape, strides, ptr = cai['typestr'], tuple(cai['shape']), cai.get('strides'), int(cai['data'][0])
+    if np.dtype(typestr) != np.dtype('<f4') or len(shape) != 2 or shape[1] != self.obs_dim:
+      raise ValueError(f'MLPPolicy: observations must be float32 of shape (rows, {self.obs_dim}), not {typestr} {tuple(shape)}')
+    pitch = self.obs_dim * 4 if strides is None else strides[0]
+    if (strides is not None and strides[1] != 4) or pitch < self.obs_dim * 4 or pitch % 16 or ptr % 16:
+      raise ValueError('MLPPolicy: observation rows must be contiguous, 16-byte aligned and a multiple of 16 bytes apart')
+    return ptr, int(shape[0]), pitch // 4
+
+  def _out(self, x, shape, what):
+    if x is None:
+      return None
+    if isinstance(x, nat.DeviceArray) and x.strides is not None and tuple(x.strides) == tuple(np.zeros(x.shape, x.dtype).strides):
+      x = nat.DeviceArray(x.ctx, x.ptr, x.shape, x.dtype)
+    try:
+      return nat.device_pointer(x, shape, self._ctx.device)
+    except ValueError as e:
+      raise ValueError(f'MLPPolicy: {what}: {e}') from None
+
+  def forward(self, obs, actions=None, logp=None, value=None, cost_value=None, deterministic=False, row0=0):
+    """One fused forward of the rows of `obs` (a device view [rows, obs_dim]) into the device views that are given: actions
+    [rows, nu], logp, value, cost_value [rows].  Actions are mean + std * z, unclamped - with deterministic=True, or without
+    `actions`, nothing is sampled: the actions are the mean and logp = -logp_const.  `draw` advances by one per sampled call.
+    row0 is added to the row index in the generator's counter (the rows of a second call that continue those of a first)."""
+    ptr, rows, pitch = self._rows(obs)
+    if rows < 1:
+      return
+    sampled = actions is not None and not deterministic
+    self._ctx.policy_forward(rows, self.hidden, self._buf, ptr, self.logp_const,
+                             d_actions=self._out(actions, (rows, self.nu), 'actions'), d_logp=self._out(logp, (rows,), 'logp'),
+                             d_value=self._out(value, (rows,), 'value'), d_cvalue=self._out(cost_value, (rows,), 'cost_value'),
+                             activation=ACTIVATIONS[self.activation], flags=0 if sampled or actions is None else nat.POLICY_MEAN,
+                             draw=self.draw, row0=row0, obs_pitch=pitch)
+    if sampled:
+      self.draw = (self.draw + 1) & 0xffffffff
+
+  def __call__(self, obs, actions):
+    """policy(obs[t], actions[t]): what RolloutBuffer.collect() asks of any policy."""
+    self.forward(obs, actions, deterministic=getattr(self, 'deterministic', False))
+
+  deterministic = False   # set on the object: act_into() and __call__ write the mean
+
+  def act_into(self, buf, t):
+    """The forward of buf.obs[t] into buf.actions[t], buf.logp[t], buf.value[t] and buf.cost_value[t]."""
+    self.forward(buf.obs[t], buf.actions[t], buf.logp[t], buf.value[t], buf.cost_value[t], deterministic=self.deterministic)
+
+  def evaluate(self, buf):
+    """After buf.collect(pi): the values of buf.obs[T] into row T of buf.value and buf.cost_value, and the values of the rows of
+    buf.final_observations() into buf.final_value and buf.final_cost_value - what buf.advantages() bootstraps from.  Joins the
+    stream once (the number of final rows comes to the host)."""
+    T = buf.T
+    self.forward(buf.obs[T], value=buf.value[T], cost_value=buf.cost_value[T])
+    rows, count = buf.final_observations()
+    if count:
+      fv, fcv = buf.final_value, buf.final_cost_value
+      self.forward(rows, value=nat.DeviceArray(fv.ctx, fv.ptr, (count,), np.float32),
+                   cost_value=nat.DeviceArray(fcv.ctx, fcv.ptr, (count,), np.float32))
+
+  def close(self):
+    c = getattr(self, '_ctx', None)
+    if c is not None and c.h and getattr(self, '_buf', None) is not None:
+      c.dev_free(self._buf)
+    self._buf = None
+    self._ctx = None
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:  # interpreter shutdown
+      pass

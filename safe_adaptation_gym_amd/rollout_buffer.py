@@ -54,6 +54,8 @@ class RolloutBuffer:
     episode [T, N, 4] f32          return, cost, length, goals met of the episode that ended; meaningful where done != 0
     final_slot [T, N] int32        where done != 0: the row of final_observations() that holds the observation the final
                                    transition reached, or -1 if the store was full; -1 elsewhere
+    value, cost_value [T+1, N], logp [T, N], final_value, final_cost_value [final_capacity] f32: owned views made on first use,
+                                   which a policy on the device fills (MLPPolicy.act_into / evaluate) and advantages() reads
   final_capacity: rows of the final-observation store; default N * (T // time_limit + 1) with a time limit, else N.  A row
   that does not fit is counted (final_dropped()), not an error.
 
@@ -143,6 +145,11 @@ class RolloutBuffer:
     return self._tm('cvalue', self.T + 1)
 
   @property
+  def logp(self):
+    """[T, N] f32: the log-probability of actions[t] under the policy that drew them (MLPPolicy.act_into writes it)."""
+    return self._tm('logp', self.T)
+
+  @property
   def final_value(self):
     return nat.DeviceArray(self._ctx, self._plane('fvalue', (self.final_capacity,)).value, (self.final_capacity,), np.float32)
 
@@ -198,10 +205,15 @@ class RolloutBuffer:
 
   def collect(self, policy):
     """begin(), then T times policy(obs[t], actions[t]) - which fills the action rows, on the device or with set_actions - and
-    step(t)."""
+    step(t).  A policy with an act_into(buf, t) method (MLPPolicy) is asked through it instead: it also writes logp[t], value[t]
+    and cost_value[t]."""
     self.begin()
+    act_into = getattr(policy, 'act_into', None)
     for t in range(self.T):
-      policy(self.obs[t], self.actions[t])
+      if act_into is not None:
+        act_into(self, t)
+      else:
+        policy(self.obs[t], self.actions[t])
       self.step(t)
 
   def wait(self):
