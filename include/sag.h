@@ -595,6 +595,93 @@ typedef struct sag_policy_desc {
 } sag_policy_desc;
 int sag_policy_forward_device(sag_ctx* ctx, const sag_policy_desc* desc);
 
+/* ---- the PPO-Lagrangian update of that MLP on the context stream (throughput mode) ----------------
+ * sag_policy_backward_device: the gradient of a clipped-surrogate actor loss, two critic losses and an entropy bonus through
+ * the network of sag_policy_forward_device, over rows stored the way the rollout buffer stores them; sag_adam_device: the
+ * optimiser step.  Both are enqueued on the context stream and return without waiting; they copy nothing to the host, record
+ * no timing events and need no installed layout (the one exception: a call that has to grow the context's workspace - the
+ * first one, or one with a larger grid or more parameters than any before - synchronises the stream once, as
+ * sag_plan_shift_device does).
+ *
+ * Inputs: n_planes planes of `pitch` >= n_rows rows each; in every plane the first n_rows rows are read, the rest is never
+ * touched.  Row g of the batch (0 <= g < n_planes * n_rows) is row g % n_rows of plane g / n_rows.
+ *   d_obs [n_planes][pitch][obs_pitch] f32 (16-byte aligned, obs_pitch a multiple of 4 and >= obs_dim; pad columns not read)
+ *   d_actions [n_planes][pitch][nu]     d_logp_old, d_adv, d_ret [n_planes][pitch]
+ *   d_cadv, d_cret [n_planes][pitch], each may be NULL: then its term is absent (cadv counts as cadv_sub; no cost critic loss,
+ *   statistic 2 is zero)                d_params as sag_policy_forward_device
+ * Output: d_grad [n_params + 8] f32 - the gradient in the parameter layout (W1 b1 W2 b2 W3 b3 std), then 8 statistics.
+ *
+ * The defined function.  Per row, with mean, v, cv the forward's chain recomputed (no activation is read from memory):
+ *   zeta[u] = (a[u] - mean[u]) / std[u]
+ *   logp = -0.5 * sum_u zeta[u]^2 - sum_u log(std[u]) - nu / 2 * log(2 pi)      (the log sum is formed on the device)
+ *   rho  = exp(logp - logp_old)
+ *   A    = adv_mul * (adv - adv_sub) - cadv_mul * (cadv - cadv_sub)
+ *   live = (A >= 0 && rho <= 1 + clip) || (A < 0 && rho >= 1 - clip)
+ *   L    = -(live ? rho : clamp(rho, 1 - clip, 1 + clip)) * A + vf_coef * 0.5 * (v - ret)^2 + cvf_coef * 0.5 * (cv - cret)^2
+ *          - ent_coef * sum_u log(std[u])
+ *   grad = scale * sum over rows of dL / dtheta for every entry of W1 b1 W2 b2 W3 b3 std (for std: the derivative with respect
+ *          to std itself, not its logarithm)
+ * A row that is not live contributes nothing through logp.  The ReLU derivative is (z > 0) on the forward's own fp32
+ * pre-activation, the tanh derivative 1 - h^2 on the forward's h.  `scale` is the caller's 1 / (rows of the whole batch), so
+ * that calls over parts of a batch add up to the batch mean.  The statistics, each times scale:
+ *   0 sum(-surrogate)   1 sum(0.5 (v - ret)^2)   2 sum(0.5 (cv - cret)^2)   3 sum(logp_old - logp)   4 rows not live
+ *   5 rows              6, 7 zero
+ * With SAG_POLICY_GRAD_ACCUMULATE all n_params + 8 words are added to what d_grad holds; without it they replace it.
+ *
+ * Determinism: the same inputs, library and device give the same bits in d_grad on every call; there are no floating-point
+ * atomics.  grid = min(ceil(n_planes * n_rows / 32), max_blocks > 0 ? min(max_blocks, 1024) : 256) persistent blocks; block b
+ * takes the tiles of 32 consecutive rows b, b + grid, ... in that order and writes one partial into a workspace owned by the
+ * context (freed with it); a final pass computes d_grad[i] = old + scale * partial[0][i] + scale * partial[1][i] + ... in
+ * ascending block order, `old` being d_grad[i] under ACCUMULATE and 0 otherwise.  The grid is a function of n_planes * n_rows
+ * and max_blocks only; the order of the sums inside a block is not part of the ABI, and unlike the forward this function is
+ * defined to a tolerance, not bit for bit (exp, log and the reciprocal are the hardware's 1 ulp-class ones).
+ *
+ * hidden: 32 ... 128 for every robot.  160 ... 256 return SAG_ERR_UNSUPPORTED (the weight-gradient accumulators of a block stay
+ * in registers; beyond 128 they do not fit).
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret or d_grad; d_obs not
+ * 16-byte or another array not 4-byte aligned; hidden not a multiple of 32 in 32 ... 256; an unknown activation or flag bit;
+ * obs_pitch < obs_dim or not a multiple of 4; n_rows < 1, n_planes < 1 or pitch < n_rows; max_blocks < 0; clip outside (0, 1);
+ * a coefficient or scale that is not finite. */
+enum sag_policy_grad_flags { SAG_POLICY_GRAD_ACCUMULATE = 1 };
+typedef struct sag_policy_grad_desc {
+  int32_t n_rows, n_planes, pitch, obs_pitch;
+  int32_t hidden, activation, flags, max_blocks;
+  float clip, vf_coef, cvf_coef, ent_coef;
+  float adv_mul, adv_sub, cadv_mul, cadv_sub;
+  float scale, reserved;
+  const float* d_params;
+  const float* d_obs;
+  const float* d_actions;
+  const float* d_logp_old;
+  const float* d_adv;
+  const float* d_ret;
+  const float* d_cadv;
+  const float* d_cret;
+  float* d_grad;
+} sag_policy_grad_desc;
+int sag_policy_backward_device(sag_ctx* ctx, const sag_policy_grad_desc* desc);
+
+/* sag_adam_device: one Adam step on n elements of d_param, d_grad, d_m and d_v, in fp32 with every operation rounded on its
+ * own (no fused multiply-add) and correctly rounded sqrt and division:
+ *   m   = fl(fl(beta1 * m) + fl(fl(1 - beta1) * g))
+ *   v   = fl(fl(beta2 * v) + fl(fl(fl(1 - beta2) * g) * g))
+ *   den = fl(sqrt(v) + eps)
+ *   p   = fl(p - fl(fl(step * m) / den))
+ *   for index >= clamp_first:  p = p > clamp_lo ? p : clamp_lo
+ * step = lr * sqrt(1 - beta2^t) / (1 - beta1^t), rounded once by the caller; clamp_first == n clamps nothing (an MLP's std sits
+ * at the end of its parameters: clamp_first = n_params - nu keeps it at or above clamp_lo).
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc or pointer, one not 4-byte aligned; n < 1; clamp_first outside [0, n]; beta1 or
+ * beta2 outside [0, 1); eps <= 0; a step or clamp_lo that is not finite. */
+typedef struct sag_adam_desc {
+  int32_t n, clamp_first;
+  float beta1, beta2, eps, step, clamp_lo, reserved;
+  float* d_param;
+  const float* d_grad;
+  float* d_m;
+  float* d_v;
+} sag_adam_desc;
+int sag_adam_device(sag_ctx* ctx, const sag_adam_desc* desc);
+
 /* ---- fork on the device (throughput mode) -------------------------------------------------------
  * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`
  * itself (a fork inside a batch) or another one, of any n_envs (a few real envs feeding many planner envs; a second context

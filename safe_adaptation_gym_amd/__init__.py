@@ -17,6 +17,9 @@ def __getattr__(name):
   if name == 'MLPPolicy':   # sag.MLPPolicy(env, hidden): a Gaussian actor-critic MLP whose forward runs on the device (policy.py)
     from safe_adaptation_gym_amd.policy import MLPPolicy
     return MLPPolicy
+  if name == 'PPOLearner':   # sag.PPOLearner(pi, buf): the PPO-Lagrangian update of an MLPPolicy on the device (learner.py)
+    from safe_adaptation_gym_amd.learner import PPOLearner
+    return PPOLearner
   raise AttributeError(f'module {__name__!r} has no attribute {name!r}')
 
 

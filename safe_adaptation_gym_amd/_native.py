@@ -37,7 +37,7 @@ EXPORTS = [
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
     'sag_episode_clear', 'sag_copy_rows_device', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
     'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device',
-    'sag_policy_forward_device'
+    'sag_policy_forward_device', 'sag_policy_backward_device', 'sag_adam_device'
 ]
 
 
@@ -75,8 +75,24 @@ class PolicyDesc(C.Structure):
           (k, C.c_void_p) for k in ('d_params', 'd_obs', 'd_actions', 'd_logp', 'd_value', 'd_cvalue')]
 
 
+class PolicyGradDesc(C.Structure):
+  """sag_policy_grad_desc (include/sag.h)."""
+  _fields_ = [(k, C.c_int32) for k in ('n_rows', 'n_planes', 'pitch', 'obs_pitch', 'hidden', 'activation', 'flags', 'max_blocks')] + [
+      (k, C.c_float) for k in ('clip', 'vf_coef', 'cvf_coef', 'ent_coef', 'adv_mul', 'adv_sub', 'cadv_mul', 'cadv_sub', 'scale', 'reserved')] + [
+          (k, C.c_void_p) for k in ('d_params', 'd_obs', 'd_actions', 'd_logp_old', 'd_adv', 'd_ret', 'd_cadv', 'd_cret', 'd_grad')]
+
+
+class AdamDesc(C.Structure):
+  """sag_adam_desc (include/sag.h)."""
+  _fields_ = [('n', C.c_int32), ('clamp_first', C.c_int32)] + [
+      (k, C.c_float) for k in ('beta1', 'beta2', 'eps', 'step', 'clamp_lo', 'reserved')] + [
+          (k, C.c_void_p) for k in ('d_param', 'd_grad', 'd_m', 'd_v')]
+
+
 POLICY_RELU, POLICY_TANH = 0, 1   # enum sag_policy_activation
 POLICY_MEAN = 1                   # enum sag_policy_flags
+POLICY_GRAD_ACCUMULATE = 1        # enum sag_policy_grad_flags
+POLICY_GRAD_STATS = 8             # words behind the gradient
 
 _lib = None
 
@@ -150,6 +166,8 @@ def load():
   lib.sag_append_rows_device.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp]
   lib.sag_gae_device.argtypes = [vp, C.POINTER(GaeDesc)]
   lib.sag_policy_forward_device.argtypes = [vp, C.POINTER(PolicyDesc)]
+  lib.sag_policy_backward_device.argtypes = [vp, C.POINTER(PolicyGradDesc)]
+  lib.sag_adam_device.argtypes = [vp, C.POINTER(AdamDesc)]
   _lib = lib
   return lib
 
@@ -531,6 +549,27 @@ class Context:
                    int(draw) & 0xffffffff, int(row0) & 0xffffffff, float(logp_const),
                    *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp, d_value, d_cvalue)])
     self._check(self.lib.sag_policy_forward_device(self.h, C.byref(d)), 'sag_policy_forward_device')
+
+  def policy_backward(self, n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale,
+                      d_cadv=None, d_cret=None, clip=0.2, vf_coef=0.5, cvf_coef=0.5, ent_coef=0.0, adv_affine=(1.0, 0.0),
+                      cadv_affine=(0.0, 0.0), activation=POLICY_RELU, flags=0, max_blocks=0, obs_pitch=None):
+    """sag_policy_backward_device: the PPO-Lagrangian gradient and 8 statistics of n_planes x n_rows stored rows (planes `pitch`
+    rows apart) into d_grad [n_params + 8], enqueued on the context stream - no wait, no host copy.  The header defines the
+    function; adv_affine = (adv_mul, adv_sub), cadv_affine likewise.  Pointers are c_void_p, ints or None."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = PolicyGradDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(hidden),
+                       int(activation), int(flags), int(max_blocks), float(clip), float(vf_coef), float(cvf_coef), float(ent_coef),
+                       float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
+                       *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
+    self._check(self.lib.sag_policy_backward_device(self.h, C.byref(d)), 'sag_policy_backward_device')
+
+  def adam(self, n, d_param, d_grad, d_m, d_v, step, beta1=0.9, beta2=0.999, eps=1e-8, clamp_first=None, clamp_lo=0.0):
+    """sag_adam_device: one Adam step on n float32 elements (the header has the chain; `step` is the bias-corrected learning
+    rate), elements from clamp_first on kept at or above clamp_lo; enqueued on the context stream."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = AdamDesc(int(n), int(n if clamp_first is None else clamp_first), float(beta1), float(beta2), float(eps), float(step),
+                 float(clamp_lo), 0.0, *[ptr(x) for x in (d_param, d_grad, d_m, d_v)])
+    self._check(self.lib.sag_adam_device(self.h, C.byref(d)), 'sag_adam_device')
 
   def fork_device(self, d_src, source=None, same_stream=False, flags=None):
     """sag_fork_device: env i takes the complete state of env d_src[i] of `source` (a Context on the same device; default:

@@ -25,6 +25,7 @@
 #include "sag_plan.hpp"
 #include "sag_buffer.hpp"
 #include "sag_policy.hpp"
+#include "sag_policy_grad.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -116,6 +117,8 @@ struct sag_ctx {
   // sag_plan_*: alive flags of a scoring rollout and the ranks of a refit ([N] each), the second buffer of sag_plan_shift_device
   uint8_t* d_palive = nullptr; int32_t* d_prank = nullptr;
   float* d_pshift = nullptr; size_t pshift_floats = 0;
+  // sag_policy_backward_device: one partial gradient per block
+  float* d_pgrad = nullptr; size_t pgrad_floats = 0;
   std::string err;
 };
 
@@ -575,7 +578,7 @@ int sag_destroy(sag_ctx* c) {
   for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   void* bufs[] = {c->S, c->I, c->G, c->d_rows, c->d_count, c->d_kind, c->L_f, c->L_i, c->st_f, c->st_i, c->st_ids, c->d_act, c->d_noise,
                   c->d_tape, c->d_obs, c->d_rew, c->d_cost, c->d_done, c->d_met, c->d_used, c->scratch, c->d_rgb, c->d_dr, c->d_dg_sched, c->d_hot,
-                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot, c->d_palive, c->d_prank, c->d_pshift};
+                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot, c->d_palive, c->d_prank, c->d_pshift, c->d_pgrad};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
@@ -1244,6 +1247,87 @@ int sag_policy_forward_device(sag_ctx* c, const sag_policy_desc* d) {
     case 7: hipLaunchKernelGGL((k_policy_forward<7>), grid, block, lds, c->stream, a); break;
     default: hipLaunchKernelGGL((k_policy_forward<8>), grid, block, lds, c->stream, a); break;
   }
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+// ---- the update (sag_policy_grad.hpp) ----
+int sag_policy_backward_device(sag_ctx* c, const sag_policy_grad_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_policy_backward_device";
+  if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
+  if (!d->d_params || !d->d_obs || !d->d_actions || !d->d_logp_old || !d->d_adv || !d->d_ret || !d->d_grad)
+    return fail(c, SAG_ERR_ARG, "%s: d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret and d_grad must be given", who);
+  if (misaligned(d->d_obs, 16) || misaligned(d->d_params, 4) || misaligned(d->d_actions, 4) || misaligned(d->d_logp_old, 4) ||
+      misaligned(d->d_adv, 4) || misaligned(d->d_ret, 4) || misaligned(d->d_cadv, 4) || misaligned(d->d_cret, 4) || misaligned(d->d_grad, 4))
+    return fail(c, SAG_ERR_ARG, "%s: a misaligned buffer (d_obs 16 bytes; the others 4)", who);
+  if (d->hidden < 32 || d->hidden > 32 * POLICY_MAX_TILES || (d->hidden & 31))
+    return fail(c, SAG_ERR_ARG, "%s: hidden = %d is not a multiple of 32 in 32 ... %d", who, d->hidden, 32 * POLICY_MAX_TILES);
+  if (d->activation != SAG_POLICY_RELU && d->activation != SAG_POLICY_TANH) return fail(c, SAG_ERR_ARG, "%s: activation = %d", who, d->activation);
+  if (d->flags & ~SAG_POLICY_GRAD_ACCUMULATE) return fail(c, SAG_ERR_ARG, "%s: unknown flag bits 0x%x", who, d->flags & ~SAG_POLICY_GRAD_ACCUMULATE);
+  if (d->obs_pitch < c->rb.obs_dim || (d->obs_pitch & 3))
+    return fail(c, SAG_ERR_ARG, "%s: obs_pitch = %d (rows of %d floats, a multiple of 4)", who, d->obs_pitch, c->rb.obs_dim);
+  if (d->n_rows < 1 || d->n_planes < 1 || d->pitch < d->n_rows)
+    return fail(c, SAG_ERR_ARG, "%s: n_rows = %d, n_planes = %d, pitch = %d", who, d->n_rows, d->n_planes, d->pitch);
+  if (d->max_blocks < 0) return fail(c, SAG_ERR_ARG, "%s: max_blocks = %d", who, d->max_blocks);
+  if (!(d->clip > 0.0f && d->clip < 1.0f)) return fail(c, SAG_ERR_ARG, "%s: clip = %g is not inside (0, 1)", who, (double)d->clip);
+  for (float x : {d->vf_coef, d->cvf_coef, d->ent_coef, d->adv_mul, d->adv_sub, d->cadv_mul, d->cadv_sub, d->scale})
+    if (!std::isfinite(x)) return fail(c, SAG_ERR_ARG, "%s: a coefficient or scale that is not finite", who);
+  if (c->rb.obs_dim > POLICY_MAX_OBS || (c->rb.obs_dim & 3) || c->rb.nu + 2 > 14)
+    return fail(c, SAG_ERR_UNSUPPORTED, "%s: obs_dim = %d, nu = %d", who, c->rb.obs_dim, c->rb.nu);
+  if (d->hidden > 32 * PGRAD_MAX_TILES)
+    return fail(c, SAG_ERR_UNSUPPORTED, "%s: hidden = %d: the backward pass is built for hidden <= %d", who, d->hidden, 32 * PGRAD_MAX_TILES);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int od = c->rb.obs_dim, nu = c->rb.nu, H = d->hidden, NO = nu + 2;
+  PolicyGradArgs a;
+  a.total = (int64_t)d->n_planes * d->n_rows;
+  a.n_rows = d->n_rows; a.pitch = d->pitch; a.obs_dim = od; a.nu = nu; a.activation = d->activation; a.obs_pitch = d->obs_pitch;
+  a.n_params = od * H + H + H * H + H + H * NO + NO + nu;
+  a.clip = d->clip; a.vf = d->vf_coef; a.cvf = d->cvf_coef; a.ent = d->ent_coef;
+  a.adv_mul = d->adv_mul; a.adv_sub = d->adv_sub; a.cadv_mul = d->cadv_mul; a.cadv_sub = d->cadv_sub;
+  a.params = d->d_params; a.obs = d->d_obs; a.actions = d->d_actions; a.logp_old = d->d_logp_old; a.adv = d->d_adv; a.ret = d->d_ret;
+  a.cadv = d->d_cadv; a.cret = d->d_cret;
+  const int grid = pgrad_grid(a.total, d->max_blocks), words = a.n_params + PGRAD_STATS;
+  const size_t need = (size_t)grid * words;
+  if (c->pgrad_floats < need) {   // (a workspace in use by the stream is not freed under it)
+    if (c->d_pgrad) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_pgrad); }
+    c->d_pgrad = nullptr; c->pgrad_floats = 0;
+    HIPCHK(c, hipMalloc(&c->d_pgrad, need * sizeof(float)));
+    c->pgrad_floats = need;
+  }
+  a.part = c->d_pgrad;
+  const size_t lds = pgrad_lds_floats(od, H) * sizeof(float);
+  const dim3 g((unsigned)grid), block(PGRAD_THREADS);
+  switch (H / 32) {
+    case 1: hipLaunchKernelGGL((k_policy_backward<1>), g, block, lds, c->stream, a); break;
+    case 2: hipLaunchKernelGGL((k_policy_backward<2>), g, block, lds, c->stream, a); break;
+    case 3: hipLaunchKernelGGL((k_policy_backward<3>), g, block, lds, c->stream, a); break;
+    default: hipLaunchKernelGGL((k_policy_backward<4>), g, block, lds, c->stream, a); break;
+  }
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_policy_grad_reduce, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, c->d_pgrad, grid, words, d->scale,
+                     (d->flags & SAG_POLICY_GRAD_ACCUMULATE) != 0, d->d_grad);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+int sag_adam_device(sag_ctx* c, const sag_adam_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d) return fail(c, SAG_ERR_ARG, "sag_adam_device: desc is NULL");
+  if (!d->d_param || !d->d_grad || !d->d_m || !d->d_v) return fail(c, SAG_ERR_ARG, "sag_adam_device: d_param, d_grad, d_m and d_v must be given");
+  if (misaligned(d->d_param, 4) || misaligned(d->d_grad, 4) || misaligned(d->d_m, 4) || misaligned(d->d_v, 4))
+    return fail(c, SAG_ERR_ARG, "sag_adam_device: a buffer that is not 4-byte aligned");
+  if (d->n < 1 || d->clamp_first < 0 || d->clamp_first > d->n) return fail(c, SAG_ERR_ARG, "sag_adam_device: n = %d, clamp_first = %d", d->n, d->clamp_first);
+  auto beta = [](float x) { return x >= 0.0f && x < 1.0f; };   // (false for a NaN)
+  if (!beta(d->beta1) || !beta(d->beta2)) return fail(c, SAG_ERR_ARG, "sag_adam_device: beta1 = %g, beta2 = %g: each in [0, 1)", (double)d->beta1, (double)d->beta2);
+  if (!(d->eps > 0.0f) || !std::isfinite(d->eps)) return fail(c, SAG_ERR_ARG, "sag_adam_device: eps = %g", (double)d->eps);
+  if (!std::isfinite(d->step) || !std::isfinite(d->clamp_lo)) return fail(c, SAG_ERR_ARG, "sag_adam_device: step = %g, clamp_lo = %g", (double)d->step, (double)d->clamp_lo);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  AdamArgs a;
+  a.n = d->n; a.clamp_first = d->clamp_first; a.beta1 = d->beta1; a.beta2 = d->beta2;
+  a.omb1 = 1.0f - d->beta1; a.omb2 = 1.0f - d->beta2; a.eps = d->eps; a.step = d->step; a.clamp_lo = d->clamp_lo;
+  a.param = d->d_param; a.grad = d->d_grad; a.m = d->d_m; a.v = d->d_v;
+  hipLaunchKernelGGL(k_adam, dim3((unsigned)((d->n + 255) / 256)), dim3(256), 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }

@@ -17,6 +17,17 @@ ACTIVATIONS = {'relu': nat.POLICY_RELU, 'tanh': nat.POLICY_TANH}
 KEYS = ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'std')
 
 
+def plane_range(view, t0, t1):
+  """Planes t0 ... t1 - 1 of a time-major device view (a RolloutBuffer's arrays), as a view of the same kind: what
+  MLPPolicy.backward takes as one minibatch."""
+  t0, t1 = int(t0), int(t1)
+  if not 0 <= t0 < t1 <= view.shape[0]:
+    raise ValueError(f'plane_range: planes {t0} ... {t1} of {view.shape[0]}')
+  strides = view.strides if view.strides is not None else np.zeros(view.shape, view.dtype).strides
+  return type(view)(view.ctx, view.ptr + t0 * strides[0], (t1 - t0,) + tuple(view.shape[1:]), view.dtype, strides=tuple(strides),
+                    base=view._base)
+
+
 class MLPPolicy:
   """pi = MLPPolicy(env, hidden=64, activation='relu', seed=0, log_std=-0.5)
 
@@ -28,6 +39,9 @@ class MLPPolicy:
   views of ONE device buffer in the ABI's layout, which a learner may overwrite in place on the context's stream (after writing
   'std' that way, call refresh() - the log-probability's constant is formed on the host).  set_params() / get_params() go
   through the host.
+
+  grad: {the keys of `params`, 'stats' [8]} - DeviceArray views of ONE buffer of n_params + 8 floats that backward() fills
+  (sag_policy_backward_device) and an optimiser reads in place (PPOLearner; Context.adam).
 
   Every method but set_params / get_params / refresh / evaluate only enqueues work: no wait, no host copy."""
 
@@ -57,6 +71,12 @@ class MLPPolicy:
     for k in KEYS:
       self.params[k] = nat.DeviceArray(c, self._buf.value + 4 * off, self.shapes[k], np.float32)
       off += int(np.prod(self.shapes[k]))
+    self._gbuf = c.dev_alloc((self.n_params + nat.POLICY_GRAD_STATS) * 4)
+    self.grad, off = {}, 0
+    for k in KEYS:
+      self.grad[k] = nat.DeviceArray(c, self._gbuf.value + 4 * off, self.shapes[k], np.float32)
+      off += int(np.prod(self.shapes[k]))
+    self.grad['stats'] = nat.DeviceArray(c, self._gbuf.value + 4 * off, (nat.POLICY_GRAD_STATS,), np.float32)
     rng = np.random.RandomState(seed)
     init = {}
     for k in KEYS[:-1]:
@@ -169,11 +189,65 @@ class MLPPolicy:
       self.forward(rows, value=nat.DeviceArray(fv.ctx, fv.ptr, (count,), np.float32),
                    cost_value=nat.DeviceArray(fcv.ctx, fcv.ptr, (count,), np.float32))
 
+  # -- the backward ------------------------------------------------------------------------------------------------------
+  def _planes(self, x, tail, what):
+    """(pointer, planes, rows, pitch in rows) of a time-major float32 device view [planes, rows] + tail whose rows are
+    contiguous and whose planes are a whole number of rows apart."""
+    if isinstance(x, nat.DeviceArray):
+      typestr, shape, strides, ptr = x.dtype.str, x.shape, x.strides, x.ptr
+    else:
+      cai = getattr(x, '__cuda_array_interface__', None)
+      if cai is None:
+        raise TypeError(f'MLPPolicy.backward: {what}: {type(x).__name__} is not a device array')
+      typestr, shape, strides, ptr = cai['typestr'], tuple(cai['shape']), cai.get('strides'), int(cai['data'][0])
+    if np.dtype(typestr) != np.dtype('<f4') or len(shape) != 2 + len(tail) or tuple(shape[2:]) != tuple(tail):
+      raise ValueError(f'MLPPolicy.backward: {what} must be float32 of shape (planes, rows{"".join(", %d" % t for t in tail)}), '
+                       f'not {typestr} {tuple(shape)}')
+    dense = np.zeros((1, 1) + tuple(tail), np.float32).strides[1:]
+    strides = np.zeros(shape, np.float32).strides if strides is None else tuple(strides)
+    if tuple(strides[1:]) != tuple(dense) or strides[0] % dense[0] or strides[0] < shape[1] * dense[0]:
+      raise ValueError(f'MLPPolicy.backward: {what}: rows must be contiguous and planes a whole number of rows apart')
+    return ptr, int(shape[0]), int(shape[1]), strides[0] // dense[0]
+
+  def backward(self, obs, actions, logp_old, adv, ret, cadv=None, cret=None, *, clip, vf_coef, cost_vf_coef, ent_coef,
+               adv_affine=(1.0, 0.0), cadv_affine=(0.0, 0.0), scale, accumulate=False):
+    """The gradient of the PPO-Lagrangian loss over stored rows into `grad` (sag_policy_backward_device; include/sag.h defines
+    the loss), enqueued on the stream.  Every input is a time-major device view [planes, rows, ...] - a RolloutBuffer's obs,
+    actions, logp and the views advantages() returns, or a range of their planes (plane_range) - and all must share planes, rows
+    and the pitch between planes; ValueError otherwise, or for a hidden size the backward does not support (> 128).  The
+    advantage is adv_affine[0] * (adv - adv_affine[1]) - cadv_affine[0] * (cadv - cadv_affine[1]); scale is 1 / (rows of the
+    whole batch); accumulate=True adds to what `grad` holds."""
+    if self.hidden > 128:
+      raise ValueError(f'MLPPolicy.backward: hidden={self.hidden}: the backward pass supports hidden <= 128')
+    given = [('obs', obs, (self.obs_dim,)), ('actions', actions, (self.nu,)), ('logp_old', logp_old, ()), ('adv', adv, ()),
+             ('ret', ret, ()), ('cadv', cadv, ()), ('cret', cret, ())]
+    ptr, geom = {}, None
+    for name, x, tail in given:
+      if x is None:
+        if name not in ('cadv', 'cret'):
+          raise ValueError(f'MLPPolicy.backward: {name} is required')
+        ptr[name] = None
+        continue
+      ptr[name], *g = self._planes(x, tail, name)
+      if geom is None:
+        geom = g
+      elif g != geom:
+        raise ValueError(f'MLPPolicy.backward: {name} has (planes, rows, pitch) = {tuple(g)}, obs has {tuple(geom)}')
+    if ptr['obs'] % 16:
+      raise ValueError('MLPPolicy.backward: observation rows must be 16-byte aligned')
+    planes, rows, pitch = geom
+    self._ctx.policy_backward(rows, planes, pitch, self.hidden, self._buf, ptr['obs'], ptr['actions'], ptr['logp_old'], ptr['adv'],
+                              ptr['ret'], self._gbuf, scale, d_cadv=ptr['cadv'], d_cret=ptr['cret'], clip=clip, vf_coef=vf_coef,
+                              cvf_coef=cost_vf_coef, ent_coef=ent_coef, adv_affine=adv_affine, cadv_affine=cadv_affine,
+                              activation=ACTIVATIONS[self.activation], flags=nat.POLICY_GRAD_ACCUMULATE if accumulate else 0)
+
   def close(self):
     c = getattr(self, '_ctx', None)
     if c is not None and c.h and getattr(self, '_buf', None) is not None:
       c.dev_free(self._buf)
-    self._buf = None
+      if getattr(self, '_gbuf', None) is not None:
+        c.dev_free(self._gbuf)
+    self._buf = self._gbuf = None
     self._ctx = None
 
   def __del__(self):
