@@ -12,7 +12,11 @@ max-over-ranks of the timed region.  The step itself never touches torch.
 A "step" = one sag_step_device() over the whole shard: action noise + clip, nstep=5
 physics substeps with contact, reward (+ goal resampling), cost, 3x16 lidar, sensors,
 observation write.  Inputs (layouts, actions) are resident in HBM before timing.
-Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the last timed step returned (obs, reward, cost,
+Prints ONE JSON line on rank 0.  A plain run does only what that headline needs: set-up, burn-in, warm-up, the K timed
+steps, the dump if asked for, the line.  --full adds everything else the benchmark measures, each a run of its own: the
+sharded Doggo / multitask line (c4), the 4096-env line, the lidar + cost kernel alone, Car / push_box, the Doggo render
+line (c2, c3, c5) and the CPU baselines; --no-c2, --no-c4 and --no-cpu-baseline drop parts of it.
+--dump-outputs DIR also writes what the last timed step returned (obs, reward, cost,
 done, goal_met of a fixed env sample) as .npy files: the inputs are seeded, so two builds can be compared output for output.
 
 Every `roofline` block names its kernels and is checked against the committed rocprofv3 summary of the SAME device
@@ -325,10 +329,12 @@ def main(argv=None, run_factory=None, emit=print):
   ap.add_argument('--task', default='go_to_goal')
   ap.add_argument('--robot', default='point', help='point (headline) | car | doggo: profile another config as the main line')
   ap.add_argument('--burn-in', type=int, default=200, help='untimed steps before warmup (the contact load depends on the state age: see checks.state_age_steps)')
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true', help='after the headline, also run every other config (c2 - c5: 4096 envs, lidar + cost kernel '
+                  'alone, Car / push_box, Doggo / multitask, Doggo render) and the CPU baselines; off by default: a plain run measures the headline only')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baselines')
   ap.add_argument('--cpu-baseline-seconds', type=float, default=12.0, help='CPU time spent on the cpu_baseline sample')
-  ap.add_argument('--no-c2', action='store_true', help='skip the 4096-env (BASELINE config 2 size) line and the other single-GPU config lines')
-  ap.add_argument('--no-c4', action='store_true', help='skip the sharded Doggo / multitask line (BASELINE config 4)')
+  ap.add_argument('--no-c2', action='store_true', help='with --full: skip the 4096-env (BASELINE config 2 size) line and the other single-GPU config lines')
+  ap.add_argument('--no-c4', action='store_true', help='with --full: skip the sharded Doggo / multitask line (BASELINE config 4)')
   ap.add_argument('--c4-envs', type=int, default=4096, help='Doggo envs per GPU of the config-4 line')
   ap.add_argument('--c4-steps', type=int, default=30)
   ap.add_argument('--dump-outputs', metavar='DIR', help='write what the headline step() returned in its last timed step to '
@@ -447,7 +453,7 @@ def main(argv=None, run_factory=None, emit=print):
 
   # BASELINE config 4 as it is stated: Doggo, multitask sampler, 4096 envs PER GPU, sharded by env index over the
   # ranks (8 x 4096 = 32768 on a node) - emitted at every world size; max over ranks like the headline
-  if not args.no_c4:
+  if args.full and not args.no_c4:
     n4, k4, w4 = args.c4_envs, args.c4_steps, 5
     r4 = run_factory('multitask', n4, device, rank, robot='doggo')
     r4.burn_in(20)
@@ -464,7 +470,7 @@ def main(argv=None, run_factory=None, emit=print):
         'roofline': doggo_roofline(ms4, n4)}
     r4.close()
 
-  if rank == 0 and world == 1 and run_factory is DeviceRun:
+  if args.full and rank == 0 and world == 1 and run_factory is DeviceRun:
     if not args.no_c2:
       c2 = DeviceRun(args.task, 4096, device, 0)
       c2.burn_in(args.burn_in)

@@ -1,5 +1,6 @@
 """bench.py --dump-outputs on a CPU stand-in for DeviceRun: what is written is the last timed step's output, --steps sets
-the number of timed steps, the env sample is fixed and within the byte budget.  The harness is tested, not the kernel."""
+the number of timed steps, the env sample is fixed and within the byte budget; a plain run makes the headline's run only and
+--full adds the others.  The harness is tested, not the kernel."""
 import json
 import os
 import sys
@@ -14,8 +15,11 @@ import bench  # noqa: E402
 class CountingRun:
   """DeviceRun's interface; the outputs of a step are a function of (env, steps taken so far)."""
 
+  made = []   # (robot, task, envs) of every run created
+
   def __init__(self, task, envs, device, rank, robot='point'):
     self.envs, self.t = envs, 0
+    CountingRun.made.append((robot, task, envs))
 
   def burn_in(self, steps):
     self.run(steps)
@@ -80,3 +84,39 @@ def test_dump_sample_is_fixed_and_within_budget(tmp_path, monkeypatch):
     np.testing.assert_array_equal(a[k], b[k])
   for k, x in _last_step(5000, 4).items():
     np.testing.assert_array_equal(a[k], x[ids.astype(np.int64)].astype(np.float32))
+
+
+HEADLINE_KEYS = {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'}
+EXTRA_KEYS = {'c2_4096_envs', 'c2_lidar_cost_only', 'c3_car_push_box', 'c4_doggo_multitask', 'c5_doggo_haul_box_rgb_4096', 'cpu_baseline'}
+
+
+def _plain(argv, monkeypatch):
+  """bench.main(argv) on the stand-in; the CPU baseline is not a run object, so it is caught where it would start."""
+  baselines = []
+  monkeypatch.setattr(bench, 'cpu_baseline', lambda *a, **k: baselines.append(a) or {'value': 0.0})
+  CountingRun.made, lines = [], []
+  bench.main(argv, run_factory=CountingRun, emit=lines.append)
+  assert len(lines) == 1
+  return json.loads(lines[0]), list(CountingRun.made), baselines
+
+
+def test_plain_run_measures_the_headline_only(monkeypatch):
+  res, made, baselines = _plain(['--gpus', '1', '--steps', '5', '--warmup', '3', '--burn-in', '2', '--envs', '64'], monkeypatch)
+  assert made == [('point', 'go_to_goal', 64)] and baselines == []
+  assert HEADLINE_KEYS <= set(res) and not EXTRA_KEYS & set(res)
+  assert res['metric'] == 'env-steps/sec (batched) Point/GoToGoal' and res['unit'] == 'env-steps/s' and res['dtype'] == 'f32'
+  assert res['higher_is_better'] is True and res['steps'] == 5 and res['warmup'] == 3
+  assert abs(res['value'] - 64 * 5 / (res['ms_per_step'] * 5e-3)) < 1e-6 * res['value']
+  # the switches that trim a --full run change nothing without it
+  res2, made2, baselines2 = _plain(['--steps', '5', '--warmup', '3', '--burn-in', '2', '--envs', '64', '--no-c2', '--no-c4', '--no-cpu-baseline'], monkeypatch)
+  assert made2 == made and baselines2 == [] and set(res2) == set(res)
+
+
+def test_full_adds_the_other_lines(monkeypatch):
+  plain, _, _ = _plain(['--steps', '5', '--warmup', '3', '--burn-in', '2', '--envs', '64'], monkeypatch)
+  res, made, _ = _plain(['--full', '--steps', '5', '--warmup', '3', '--burn-in', '2', '--envs', '64', '--c4-envs', '12', '--c4-steps', '2'], monkeypatch)
+  # on a stand-in only the sharded Doggo / multitask line follows (the single-GPU lines and the CPU baselines need DeviceRun)
+  assert made == [('point', 'go_to_goal', 64), ('doggo', 'multitask', 12)]
+  assert set(res) == set(plain) | {'c4_doggo_multitask'} and res['c4_doggo_multitask']['steps'] == 2
+  _, made, _ = _plain(['--full', '--no-c4', '--steps', '5', '--warmup', '3', '--burn-in', '2', '--envs', '64'], monkeypatch)
+  assert made == [('point', 'go_to_goal', 64)]

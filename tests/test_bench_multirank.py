@@ -59,7 +59,7 @@ _dist.barrier = _late_barrier
 
 lines = []
 bench.main(['--gpus', '2', '--steps', '6', '--warmup', '2', '--burn-in', '1', '--envs', '48',
-            '--no-cpu-baseline', '--no-c2', '--c4-envs', '12', '--c4-steps', '2'], run_factory=OracleRun, emit=lines.append)
+            '--full', '--no-cpu-baseline', '--no-c2', '--c4-envs', '12', '--c4-steps', '2'], run_factory=OracleRun, emit=lines.append)
 if int(os.environ['RANK']) == 0:
   open(os.path.join(%(out)r, 'line.json'), 'w').write('\n'.join(lines))
 else:
@@ -104,7 +104,7 @@ def test_two_rank_gloo_bench(tmp_path):
   r1 = json.loads((tmp_path / 'rank1_point.json').read_text())
   assert r0['ids'] == [0, 47] and r1['ids'] == [48, 95]
   assert r0['steps'] == r1['steps'] == 1 + 2 + 6
-  # BASELINE config 4 is the config that names 8 GPUs: the sharded Doggo / multitask line is part of every --gpus N run
+  # BASELINE config 4 is the config that names 8 GPUs: the sharded Doggo / multitask line is part of every --gpus N --full run
   c4 = res['c4_doggo_multitask']
   assert c4['n_gpus'] == 2 and c4['envs_per_gpu'] == 12 and c4['global_envs'] == 24 and c4['scaling'] == 'weak'
   assert c4['env_id_ranges_per_rank'] == [[0, 12], [12, 24]] and len(c4['kernel_ms_per_rank']) == 2

@@ -43,7 +43,7 @@ if json_for:
   sys.path.insert(0, root)
   import bench
   doc = {'src_sha16': bench.source_sha16(), 'bench_py_sha16': hashlib.sha256(open(os.path.join(root, 'bench.py'), 'rb').read()).hexdigest()[:16],
-         'summary': json_for, 'command': 'FULL=1 tools/prof.sh (rocprofv3 --kernel-trace --stats + PMC passes over the default bench.py)',
+         'summary': json_for, 'command': 'FULL=1 tools/prof.sh (rocprofv3 --kernel-trace --stats + PMC passes over bench.py --full)',
          'kernels': kernels, 'doggo_flops_per_env_step': flops if len(flops) == 2 else None}
   json.dump(doc, open(os.path.join(root, 'profiles', 'kernels.json'), 'w'), indent=1)
   print('== wrote profiles/kernels.json for sources', doc['src_sha16'], 'with', len(kernels), 'kernels')
