@@ -682,6 +682,110 @@ typedef struct sag_adam_desc {
 } sag_adam_desc;
 int sag_adam_device(sag_ctx* ctx, const sag_adam_desc* desc);
 
+/* ---- what a learner needs around the backward pass: moments, the mixed advantage, the multiplier, the clip ----------
+ * Four functions over device arrays whose results stay on the device for a later call on the same stream.  Each is enqueued on
+ * the context stream and returns without waiting; none copies to the host, records timing events or needs an installed layout
+ * (the one exception, as above: a call of sag_moments_device or sag_grad_clip_device that has to grow the context's workspace
+ * - the first one, or one with a larger grid than any before - synchronises the stream once).  No floating-point atomics: the
+ * same inputs, library and device give the same bits on every call.
+ *
+ * Pitched arrays: n_planes planes of `pitch` >= n_rows rows; logical element e (0 <= e < n_planes * n_rows) is row
+ * r = e % n_rows of plane p = e / n_rows.  Pad rows (r >= n_rows) are never read or written.
+ *
+ * The reductions' grid rule (sag_moments_device, sag_grad_clip_device): a block's unit of work is a chunk of 4096 consecutive
+ * logical elements; grid = min(ceil(elements / 4096), max_blocks > 0 ? min(max_blocks, 1024) : 256) blocks of 256 threads;
+ * block b takes the chunks b, b + grid, ... in that order and writes one partial (an fp32 sum, and an integer count) into a
+ * workspace owned by the context (freed with it); the partials are then added in ascending block order.  The grid is a
+ * function of the element count and max_blocks only.  The order of the sums inside a block is not part of the ABI, so the two
+ * reductions are defined to a tolerance, not bit for bit.
+ *
+ * sag_moments_device: count, mean, population variance and reciprocal deviation of one column of a pitched array.
+ *   d_x     f32; element (p, r) is at float offset (p * pitch + r) * stride.  stride = 1 for a plain [n_planes][pitch] array
+ *           (then it is streamed with 16-byte loads wherever four elements of one plane start at a 16-byte boundary);
+ *           stride = 4 with d_x = episode + 1 reads the cost column of the rollout buffer's [T][pitch][4] episode rows.  The
+ *           other columns of a strided row are never read.
+ *   d_mask  [n_planes][pitch] u8 or NULL: element (p, r) counts where its byte is non-zero (with NULL: every element).  An
+ *           element that does not count is never read into the arithmetic: a NaN there, in a pad row or in another column
+ *           does not reach the output.
+ *   d_out   [4] f32 = {count, mean, var, rstd}:
+ *             count  the counting elements, accumulated as integers and converted to f32 once
+ *             mean   sum(x) / count
+ *             var    sum((x - mean)^2) / count, a second pass over the array that reads the fp32 mean the first one wrote
+ *             rstd   1 / (sqrt(var) + eps), sqrt and the division correctly rounded
+ *           count == 0 gives {0, 0, 0, 0}.
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc, d_x or d_out; d_x or d_out not 4-byte aligned; n_rows, n_planes or
+ * stride < 1; pitch < n_rows; n_planes * n_rows >= 2^31; max_blocks < 0; eps negative or not finite. */
+typedef struct sag_moments_desc {
+  int32_t n_rows, n_planes, pitch, stride;
+  int32_t max_blocks, reserved;
+  float eps, reserved_f;
+  const float* d_x;
+  const uint8_t* d_mask;
+  float* d_out;
+} sag_moments_desc;
+int sag_moments_device(sag_ctx* ctx, const sag_moments_desc* desc);
+
+/* sag_advantage_mix_device: the advantage the backward pass is given, elementwise over [n_planes][pitch] f32 arrays and
+ * defined bit for bit - every operation rounded on its own, no fused multiply-add:
+ *   a = adv;   adv_mode 1: a = fl(a - m_a);   adv_mode 2: a = fl(fl(a - m_a) * s_a)
+ *   c = cadv;  cadv_mode likewise with m_c, s_c
+ *   out = d_cadv ? fl(a - fl(lam * c)) : a
+ * m_a, s_a are words 1 and 3 (mean, rstd) of d_adv_mom, m_c, s_c those of d_cadv_mom: arrays as sag_moments_device writes
+ * them, required where the mode is above 0 (d_cadv_mom only with d_cadv).  lam = d_lambda ? d_lambda[0] : cost_weight - word
+ * 0 of sag_lagrange_device's state is such a d_lambda.  Modes: 0 raw, 1 centred, 2 standardised.  d_out may be d_adv or
+ * d_cadv itself (an element is read before it is written) but may not overlap them otherwise.
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc, d_adv or d_out; a moments array missing for its mode; a pointer not 4-byte
+ * aligned; n_rows or n_planes < 1; pitch < n_rows; n_planes * n_rows >= 2^31; a mode outside 0 ... 2; a cost_weight that is not
+ * finite. */
+enum sag_advantage_mode { SAG_ADV_RAW = 0, SAG_ADV_CENTER = 1, SAG_ADV_STANDARDIZE = 2 };
+typedef struct sag_advantage_mix_desc {
+  int32_t n_rows, n_planes, pitch, reserved;
+  int32_t adv_mode, cadv_mode;
+  float cost_weight, reserved_f;
+  const float* d_adv;
+  const float* d_cadv;      /* NULL: no cost term */
+  const float* d_adv_mom;
+  const float* d_cadv_mom;
+  const float* d_lambda;    /* NULL: cost_weight */
+  float* d_out;
+} sag_advantage_mix_desc;
+int sag_advantage_mix_device(sag_ctx* ctx, const sag_advantage_mix_desc* desc);
+
+/* sag_lagrange_device: one projected ascent step of the Lagrange multiplier, bit for bit (one small launch).
+ *   d_mom    [4] f32: the moments of the costs of the episodes that ended (sag_moments_device over the episode rows' cost
+ *            column under the `done` mask); words 0 (count) and 1 (mean) are read
+ *   d_state  [4] f32 = {lambda, last mean cost, last episode count, updates taken}
+ * With count > 0:  t = fl(lambda + fl(lr * fl(mean - budget)));  t = t > 0 ? t : 0;  lambda = t < lambda_max ? t : lambda_max
+ * (a NaN t becomes 0); word 1 = mean, word 2 = count, word 3 = fl(word 3 + 1).
+ * With count == 0 only word 2 becomes 0: lambda, the last mean and the number of updates stay.
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc, d_mom or d_state, one not 4-byte aligned; lr or budget not finite; lr < 0;
+ * lambda_max < 0 or NaN (+infinity is allowed: no upper clamp). */
+typedef struct sag_lagrange_desc {
+  float lr, budget, lambda_max, reserved;
+  const float* d_mom;
+  float* d_state;
+} sag_lagrange_desc;
+int sag_lagrange_device(sag_ctx* ctx, const sag_lagrange_desc* desc);
+
+/* sag_grad_clip_device: global-norm clipping of d_grad[0 ... n) in place, the clip_grad_norm_ convention:
+ *   norm   = sqrt(sum g^2)                        (the grid rule above over n elements; sqrt correctly rounded)
+ *   factor = min(1, max_norm / (norm + 1e-6))     (fp32, the division correctly rounded)
+ *   g      = fl(g * factor);  with factor == 1 nothing is written and every bit of d_grad stays
+ *   d_out  [2] f32 = {norm, factor}; it must not overlap d_grad[0 ... n)
+ * Words of d_grad at and behind n are not touched (the learner passes n_params: the 8 statistics behind the gradient stay).
+ * A norm that is not finite is not special-cased, as in the convention: an infinite norm gives factor 0 (finite elements
+ * become 0, infinite ones NaN), a NaN norm gives a NaN factor and with it NaN in every element.
+ * Two launches: the partials; then every block adds them in ascending order and scales the chunks that are its own.
+ * SAG_ERR_ARG with nothing enqueued: a NULL desc, d_grad or d_out, one not 4-byte aligned; n < 1; max_blocks < 0; max_norm
+ * negative or not finite; d_out inside d_grad[0 ... n). */
+typedef struct sag_grad_clip_desc {
+  int32_t n, max_blocks;
+  float max_norm, reserved;
+  float* d_grad;
+  float* d_out;
+} sag_grad_clip_desc;
+int sag_grad_clip_device(sag_ctx* ctx, const sag_grad_clip_desc* desc);
+
 /* ---- fork on the device (throughput mode) -------------------------------------------------------
  * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`
  * itself (a fork inside a batch) or another one, of any n_envs (a few real envs feeding many planner envs; a second context

@@ -37,7 +37,8 @@ EXPORTS = [
     'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
     'sag_episode_clear', 'sag_copy_rows_device', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
     'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device',
-    'sag_policy_forward_device', 'sag_policy_backward_device', 'sag_adam_device'
+    'sag_policy_forward_device', 'sag_policy_backward_device', 'sag_adam_device',
+    'sag_moments_device', 'sag_advantage_mix_device', 'sag_lagrange_device', 'sag_grad_clip_device'
 ]
 
 
@@ -89,7 +90,32 @@ class AdamDesc(C.Structure):
           (k, C.c_void_p) for k in ('d_param', 'd_grad', 'd_m', 'd_v')]
 
 
+class MomentsDesc(C.Structure):
+  """sag_moments_desc (include/sag.h)."""
+  _fields_ = [(k, C.c_int32) for k in ('n_rows', 'n_planes', 'pitch', 'stride', 'max_blocks', 'reserved')] + [
+      ('eps', C.c_float), ('reserved_f', C.c_float)] + [(k, C.c_void_p) for k in ('d_x', 'd_mask', 'd_out')]
+
+
+class AdvantageMixDesc(C.Structure):
+  """sag_advantage_mix_desc (include/sag.h)."""
+  _fields_ = [(k, C.c_int32) for k in ('n_rows', 'n_planes', 'pitch', 'reserved', 'adv_mode', 'cadv_mode')] + [
+      ('cost_weight', C.c_float), ('reserved_f', C.c_float)] + [
+          (k, C.c_void_p) for k in ('d_adv', 'd_cadv', 'd_adv_mom', 'd_cadv_mom', 'd_lambda', 'd_out')]
+
+
+class LagrangeDesc(C.Structure):
+  """sag_lagrange_desc (include/sag.h)."""
+  _fields_ = [(k, C.c_float) for k in ('lr', 'budget', 'lambda_max', 'reserved')] + [(k, C.c_void_p) for k in ('d_mom', 'd_state')]
+
+
+class GradClipDesc(C.Structure):
+  """sag_grad_clip_desc (include/sag.h)."""
+  _fields_ = [('n', C.c_int32), ('max_blocks', C.c_int32), ('max_norm', C.c_float), ('reserved', C.c_float)] + [
+      (k, C.c_void_p) for k in ('d_grad', 'd_out')]
+
+
 POLICY_RELU, POLICY_TANH = 0, 1   # enum sag_policy_activation
+ADV_RAW, ADV_CENTER, ADV_STANDARDIZE = 0, 1, 2   # enum sag_advantage_mode
 POLICY_MEAN = 1                   # enum sag_policy_flags
 POLICY_GRAD_ACCUMULATE = 1        # enum sag_policy_grad_flags
 POLICY_GRAD_STATS = 8             # words behind the gradient
@@ -168,6 +194,10 @@ def load():
   lib.sag_policy_forward_device.argtypes = [vp, C.POINTER(PolicyDesc)]
   lib.sag_policy_backward_device.argtypes = [vp, C.POINTER(PolicyGradDesc)]
   lib.sag_adam_device.argtypes = [vp, C.POINTER(AdamDesc)]
+  lib.sag_moments_device.argtypes = [vp, C.POINTER(MomentsDesc)]
+  lib.sag_advantage_mix_device.argtypes = [vp, C.POINTER(AdvantageMixDesc)]
+  lib.sag_lagrange_device.argtypes = [vp, C.POINTER(LagrangeDesc)]
+  lib.sag_grad_clip_device.argtypes = [vp, C.POINTER(GradClipDesc)]
   _lib = lib
   return lib
 
@@ -570,6 +600,37 @@ class Context:
     d = AdamDesc(int(n), int(n if clamp_first is None else clamp_first), float(beta1), float(beta2), float(eps), float(step),
                  float(clamp_lo), 0.0, *[ptr(x) for x in (d_param, d_grad, d_m, d_v)])
     self._check(self.lib.sag_adam_device(self.h, C.byref(d)), 'sag_adam_device')
+
+  def moments(self, n_rows, n_planes, pitch, d_x, d_out, d_mask=None, stride=1, eps=1e-8, max_blocks=0):
+    """sag_moments_device: d_out[4] = {count, mean, var, 1 / (sqrt(var) + eps)} of the n_planes x n_rows elements of d_x (planes
+    `pitch` rows apart, elements `stride` floats apart) whose byte of d_mask [n_planes][pitch] is non-zero (None: all); enqueued
+    on the context stream, the result stays on the device."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = MomentsDesc(int(n_rows), int(n_planes), int(pitch), int(stride), int(max_blocks), 0, float(eps), 0.0, ptr(d_x), ptr(d_mask), ptr(d_out))
+    self._check(self.lib.sag_moments_device(self.h, C.byref(d)), 'sag_moments_device')
+
+  def advantage_mix(self, n_rows, n_planes, pitch, d_adv, d_out, d_cadv=None, adv_mode=ADV_RAW, cadv_mode=ADV_RAW, d_adv_mom=None,
+                    d_cadv_mom=None, d_lambda=None, cost_weight=0.0):
+    """sag_advantage_mix_device: d_out = norm(adv) - lambda * norm(cadv) elementwise (the header has the chain), the moments
+    arrays as moments() writes them, lambda = d_lambda[0] or cost_weight; enqueued on the context stream."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = AdvantageMixDesc(int(n_rows), int(n_planes), int(pitch), 0, int(adv_mode), int(cadv_mode), float(cost_weight), 0.0,
+                         *[ptr(x) for x in (d_adv, d_cadv, d_adv_mom, d_cadv_mom, d_lambda, d_out)])
+    self._check(self.lib.sag_advantage_mix_device(self.h, C.byref(d)), 'sag_advantage_mix_device')
+
+  def lagrange(self, d_mom, d_state, lr, budget, lambda_max=float('inf')):
+    """sag_lagrange_device: d_state[4] = {lambda, mean cost, episodes, updates} takes one step lambda += lr * (mean - budget),
+    kept in [0, lambda_max], from the moments at d_mom (no step where their count is 0); enqueued on the context stream."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = LagrangeDesc(float(lr), float(budget), float(lambda_max), 0.0, ptr(d_mom), ptr(d_state))
+    self._check(self.lib.sag_lagrange_device(self.h, C.byref(d)), 'sag_lagrange_device')
+
+  def grad_clip(self, n, d_grad, d_out, max_norm, max_blocks=0):
+    """sag_grad_clip_device: d_grad[0 ... n) scaled in place by min(1, max_norm / (norm + 1e-6)), d_out[2] = {norm, factor};
+    enqueued on the context stream."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = GradClipDesc(int(n), int(max_blocks), float(max_norm), 0.0, ptr(d_grad), ptr(d_out))
+    self._check(self.lib.sag_grad_clip_device(self.h, C.byref(d)), 'sag_grad_clip_device')
 
   def fork_device(self, d_src, source=None, same_stream=False, flags=None):
     """sag_fork_device: env i takes the complete state of env d_src[i] of `source` (a Context on the same device; default:

@@ -26,6 +26,7 @@
 #include "sag_buffer.hpp"
 #include "sag_policy.hpp"
 #include "sag_policy_grad.hpp"
+#include "sag_learner.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -119,6 +120,8 @@ struct sag_ctx {
   float* d_pshift = nullptr; size_t pshift_floats = 0;
   // sag_policy_backward_device: one partial gradient per block
   float* d_pgrad = nullptr; size_t pgrad_floats = 0;
+  // sag_moments_device, sag_grad_clip_device: one (sum, count) partial per block
+  float* d_lpart = nullptr; size_t lpart_blocks = 0;
   std::string err;
 };
 
@@ -578,7 +581,7 @@ int sag_destroy(sag_ctx* c) {
   for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   void* bufs[] = {c->S, c->I, c->G, c->d_rows, c->d_count, c->d_kind, c->L_f, c->L_i, c->st_f, c->st_i, c->st_ids, c->d_act, c->d_noise,
                   c->d_tape, c->d_obs, c->d_rew, c->d_cost, c->d_done, c->d_met, c->d_used, c->scratch, c->d_rgb, c->d_dr, c->d_dg_sched, c->d_hot,
-                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot, c->d_palive, c->d_prank, c->d_pshift, c->d_pgrad};
+                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot, c->d_palive, c->d_prank, c->d_pshift, c->d_pgrad, c->d_lpart};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
@@ -1328,6 +1331,126 @@ int sag_adam_device(sag_ctx* c, const sag_adam_desc* d) {
   a.omb1 = 1.0f - d->beta1; a.omb2 = 1.0f - d->beta2; a.eps = d->eps; a.step = d->step; a.clamp_lo = d->clamp_lo;
   a.param = d->d_param; a.grad = d->d_grad; a.m = d->d_m; a.v = d->d_v;
   hipLaunchKernelGGL(k_adam, dim3((unsigned)((d->n + 255) / 256)), dim3(256), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+// ---- moments, the mixed advantage, the multiplier, the clip (sag_learner.hpp) ----
+namespace {
+
+// the partials of `grid` blocks: [grid] f32 sums, then [grid] i32 counts (a workspace in use by the stream is not freed under it)
+int ensure_lpart(sag_ctx* c, int grid) {
+  if (c->lpart_blocks >= (size_t)grid) return 0;
+  if (c->d_lpart) { HIPCHK(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->d_lpart); }
+  c->d_lpart = nullptr; c->lpart_blocks = 0;
+  HIPCHK(c, hipMalloc(&c->d_lpart, (size_t)grid * 2 * sizeof(float)));
+  c->lpart_blocks = (size_t)grid;
+  return 0;
+}
+
+bool span_ok(int32_t n_rows, int32_t n_planes, int32_t pitch) {
+  return n_rows >= 1 && n_planes >= 1 && pitch >= n_rows && (int64_t)n_planes * n_rows < ((int64_t)1 << 31);
+}
+
+}  // namespace
+
+int sag_moments_device(sag_ctx* c, const sag_moments_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_moments_device";
+  if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
+  if (!d->d_x || !d->d_out) return fail(c, SAG_ERR_ARG, "%s: d_x and d_out must be given", who);
+  if (misaligned(d->d_x, 4) || misaligned(d->d_out, 4)) return fail(c, SAG_ERR_ARG, "%s: d_x or d_out is not 4-byte aligned", who);
+  if (!span_ok(d->n_rows, d->n_planes, d->pitch) || d->stride < 1)
+    return fail(c, SAG_ERR_ARG, "%s: n_rows = %d, n_planes = %d, pitch = %d, stride = %d (n_planes * n_rows below 2^31)", who, d->n_rows,
+                d->n_planes, d->pitch, d->stride);
+  if (d->max_blocks < 0) return fail(c, SAG_ERR_ARG, "%s: max_blocks = %d", who, d->max_blocks);
+  if (!std::isfinite(d->eps) || d->eps < 0.0f) return fail(c, SAG_ERR_ARG, "%s: eps = %g", who, (double)d->eps);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int64_t total = (int64_t)d->n_planes * d->n_rows;
+  const int grid = learn_grid(total, d->max_blocks);
+  if (int rc = ensure_lpart(c, grid)) return rc;
+  LearnPartialArgs a;
+  a.span.total = (uint32_t)total; a.span.n_rows = (uint32_t)d->n_rows; a.span.pitch = (uint32_t)d->pitch; a.span.stride = (uint32_t)d->stride;
+  a.x_mis = (uint32_t)((reinterpret_cast<uintptr_t>(d->d_x) >> 2) & 3); a.m_mis = (uint32_t)(reinterpret_cast<uintptr_t>(d->d_mask) & 3);
+  a.x = d->d_x; a.mask = d->d_mask; a.mom = d->d_out;
+  a.part_sum = c->d_lpart; a.part_cnt = reinterpret_cast<int32_t*>(c->d_lpart + grid);
+  const dim3 g((unsigned)grid), block(LEARN_THREADS);
+  hipLaunchKernelGGL((k_learn_partial<0>), g, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_moments_final, dim3(1), block, 0, c->stream, a.part_sum, a.part_cnt, grid, 0, d->eps, d->d_out);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL((k_learn_partial<1>), g, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_moments_final, dim3(1), block, 0, c->stream, a.part_sum, a.part_cnt, grid, 1, d->eps, d->d_out);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+int sag_advantage_mix_device(sag_ctx* c, const sag_advantage_mix_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_advantage_mix_device";
+  if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
+  if (!d->d_adv || !d->d_out) return fail(c, SAG_ERR_ARG, "%s: d_adv and d_out must be given", who);
+  if (d->adv_mode < 0 || d->adv_mode > 2 || d->cadv_mode < 0 || d->cadv_mode > 2)
+    return fail(c, SAG_ERR_ARG, "%s: adv_mode = %d, cadv_mode = %d: each 0 (raw), 1 (centred) or 2 (standardised)", who, d->adv_mode, d->cadv_mode);
+  if ((d->adv_mode > 0 && !d->d_adv_mom) || (d->d_cadv && d->cadv_mode > 0 && !d->d_cadv_mom))
+    return fail(c, SAG_ERR_ARG, "%s: a mode above 0 needs its moments array", who);
+  if (misaligned(d->d_adv, 4) || misaligned(d->d_cadv, 4) || misaligned(d->d_adv_mom, 4) || misaligned(d->d_cadv_mom, 4) ||
+      misaligned(d->d_lambda, 4) || misaligned(d->d_out, 4))
+    return fail(c, SAG_ERR_ARG, "%s: a buffer that is not 4-byte aligned", who);
+  if (!span_ok(d->n_rows, d->n_planes, d->pitch))
+    return fail(c, SAG_ERR_ARG, "%s: n_rows = %d, n_planes = %d, pitch = %d (n_planes * n_rows below 2^31)", who, d->n_rows, d->n_planes, d->pitch);
+  if (!std::isfinite(d->cost_weight)) return fail(c, SAG_ERR_ARG, "%s: cost_weight is not finite", who);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int64_t total = (int64_t)d->n_planes * d->n_rows;
+  MixArgs a;
+  a.span.total = (uint32_t)total; a.span.n_rows = (uint32_t)d->n_rows; a.span.pitch = (uint32_t)d->pitch; a.span.stride = 1;
+  a.mis = (misaligned(d->d_adv, 16) || misaligned(d->d_cadv, 16) || misaligned(d->d_out, 16)) ? 1u : 0u;
+  a.adv_mode = d->adv_mode; a.cadv_mode = d->cadv_mode; a.cost_weight = d->cost_weight;
+  a.adv = d->d_adv; a.cadv = d->d_cadv; a.adv_mom = d->d_adv_mom; a.cadv_mom = d->d_cadv_mom; a.lambda = d->d_lambda; a.out = d->d_out;
+  const int64_t quads = (total + 3) / 4;
+  hipLaunchKernelGGL(k_advantage_mix, dim3((unsigned)((quads + LEARN_THREADS - 1) / LEARN_THREADS)), dim3(LEARN_THREADS), 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+int sag_lagrange_device(sag_ctx* c, const sag_lagrange_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_lagrange_device";
+  if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
+  if (!d->d_mom || !d->d_state) return fail(c, SAG_ERR_ARG, "%s: d_mom and d_state must be given", who);
+  if (misaligned(d->d_mom, 4) || misaligned(d->d_state, 4)) return fail(c, SAG_ERR_ARG, "%s: d_mom or d_state is not 4-byte aligned", who);
+  if (!std::isfinite(d->lr) || !std::isfinite(d->budget) || d->lr < 0.0f) return fail(c, SAG_ERR_ARG, "%s: lr = %g, budget = %g", who, (double)d->lr, (double)d->budget);
+  if (!(d->lambda_max >= 0.0f)) return fail(c, SAG_ERR_ARG, "%s: lambda_max = %g", who, (double)d->lambda_max);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(k_lagrange, dim3(1), dim3(WAVE), 0, c->stream, d->d_mom, d->lr, d->budget, d->lambda_max, d->d_state);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+int sag_grad_clip_device(sag_ctx* c, const sag_grad_clip_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_grad_clip_device";
+  if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
+  if (!d->d_grad || !d->d_out) return fail(c, SAG_ERR_ARG, "%s: d_grad and d_out must be given", who);
+  if (misaligned(d->d_grad, 4) || misaligned(d->d_out, 4)) return fail(c, SAG_ERR_ARG, "%s: d_grad or d_out is not 4-byte aligned", who);
+  if (d->n < 1) return fail(c, SAG_ERR_ARG, "%s: n = %d", who, d->n);
+  if (d->max_blocks < 0) return fail(c, SAG_ERR_ARG, "%s: max_blocks = %d", who, d->max_blocks);
+  if (!std::isfinite(d->max_norm) || d->max_norm < 0.0f) return fail(c, SAG_ERR_ARG, "%s: max_norm = %g", who, (double)d->max_norm);
+  const uintptr_t g0 = reinterpret_cast<uintptr_t>(d->d_grad), o0 = reinterpret_cast<uintptr_t>(d->d_out);
+  if (o0 + 2 * sizeof(float) > g0 && o0 < g0 + (size_t)d->n * sizeof(float)) return fail(c, SAG_ERR_ARG, "%s: d_out lies inside d_grad[0 ... n)", who);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  const int grid = learn_grid(d->n, d->max_blocks);
+  if (int rc = ensure_lpart(c, grid)) return rc;
+  LearnPartialArgs a;
+  a.span.total = (uint32_t)d->n; a.span.n_rows = (uint32_t)d->n; a.span.pitch = (uint32_t)d->n; a.span.stride = 1;
+  a.x_mis = (uint32_t)((reinterpret_cast<uintptr_t>(d->d_grad) >> 2) & 3); a.m_mis = 0;
+  a.x = d->d_grad; a.mask = nullptr; a.mom = nullptr;
+  a.part_sum = c->d_lpart; a.part_cnt = reinterpret_cast<int32_t*>(c->d_lpart + grid);
+  const dim3 g((unsigned)grid), block(LEARN_THREADS);
+  hipLaunchKernelGGL((k_learn_partial<2>), g, block, 0, c->stream, a);
+  HIPCHK(c, hipGetLastError());
+  hipLaunchKernelGGL(k_grad_clip_scale, g, block, 0, c->stream, a.part_sum, grid, d->max_norm, (uint32_t)d->n, d->d_grad, d->d_out);
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }
