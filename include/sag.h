@@ -786,6 +786,67 @@ typedef struct sag_grad_clip_desc {
 } sag_grad_clip_desc;
 int sag_grad_clip_device(sag_ctx* ctx, const sag_grad_clip_desc* desc);
 
+/* ---- observation normalisation on the context stream (throughput mode) ----------------------------
+ * Running per-column moments of stored observation rows, the table made from them, and the forward and backward of the MLP
+ * above with every observation element normalised where it is staged - no separate normalising pass writes or re-reads a row.
+ * Each of the three functions is enqueued on the context stream and returns without waiting; none copies to the host, records
+ * timing events or needs an installed layout (the one exception, as above: the first sag_obs_stats_device of a context
+ * allocates its workspace; sag_policy_backward_norm_device shares sag_policy_backward_device's).  No floating-point atomics.
+ *
+ * sag_obs_stats_device: the moments of a batch of rows, merged into a running state, and the table of that state.
+ *   d_obs    [n_planes][pitch][obs_pitch] f32, 16-byte aligned, obs_pitch >= obs_dim (the context's robot's) and a multiple
+ *            of 4.  The first n_rows rows of every plane count; pad rows and pad columns are never read into a register that
+ *            the arithmetic uses: a NaN there does not reach the output.
+ *   d_state  [1 + 2 obs_dim] f64 = {count, mean[obs_dim], M2[obs_dim]}, 8-byte aligned, owned by the caller; all zeros is the
+ *            empty state.
+ *   d_table  [2][obs_dim] f32 = the mean row, then the rstd row; 16-byte aligned.
+ * The defined function, per column k, with n_b = n_planes * n_rows:
+ *   mean_b = sum(x) / n_b                                   s = (float)mean_b
+ *   M2_b   = max(0, sum((x - s)^2) - n_b * (mean_b - s)^2)  a second pass over the array (the two-pass form of
+ *            sag_moments_device; the shift s is what a block can subtract in fp32, the correction term restores mean_b)
+ * Inside a block the sums are fp32 (x - s and its square each rounded); the per-block partials are added in ascending block
+ * order in fp64, and everything from there on is fp64 with every operation rounded on its own:
+ *   n = n_a + n_b    w = n_b / n    delta = mean_b - mean_a
+ *   mean = mean_a + delta * w                               M2 = (M2_a + M2_b) + (delta * delta) * (n_a * w)
+ * (Chan et al.; an empty state has w = 1 and takes the batch's moments exactly).  Then, given the state, bit for bit:
+ *   table.mean[k] = (float)mean      table.rstd[k] = (float)(1.0 / sqrt(M2 / n + (double)eps))
+ * the (x - mean) / sqrt(var + eps) convention with the population variance; the fp64 sqrt and division are correctly rounded.
+ * A count that is not above 0 after the call writes mean 0 and rstd 1 (the identity).
+ * With SAG_OBS_STATS_TABLE_ONLY in flags d_obs may be NULL and is not read, the state is not touched and the table is
+ * rewritten from it (n_rows, n_planes, pitch, obs_pitch and max_blocks are ignored): what a checkpoint restore uses, so that
+ * the table always comes from the same device arithmetic.
+ * The grid rule: a block's unit of work is a chunk of 1024 consecutive logical rows (row e is row e % n_rows of plane
+ * e / n_rows); grid = min(ceil(n_b / 1024), max_blocks > 0 ? min(max_blocks, 1024) : 1024) blocks of 256 threads; block b takes
+ * the chunks b, b + grid, ... in that order and writes one [obs_dim] partial per pass into a workspace owned by the context
+ * (freed with it).  The order of the sums inside a block is not part of the ABI, so the moments are defined to a tolerance;
+ * the same inputs, library and device give the same bits on every call.
+ * SAG_ERR_ARG with nothing enqueued and state and table untouched: a NULL desc, d_state or d_table; a NULL d_obs without
+ * TABLE_ONLY; d_obs or d_table not 16-byte, d_state not 8-byte aligned; n_rows or n_planes < 1; pitch < n_rows;
+ * n_planes * n_rows >= 2^31; obs_pitch < obs_dim or not a multiple of 4; max_blocks < 0; eps not finite or <= 0; an unknown
+ * flag bit. */
+enum sag_obs_stats_flags { SAG_OBS_STATS_TABLE_ONLY = 1 };
+typedef struct sag_obs_stats_desc {
+  int32_t n_rows, n_planes, pitch, obs_pitch;
+  int32_t max_blocks, flags;
+  float eps, reserved;
+  const float* d_obs;
+  double* d_state;
+  float* d_table;
+} sag_obs_stats_desc;
+int sag_obs_stats_device(sag_ctx* ctx, const sag_obs_stats_desc* desc);
+
+/* sag_policy_forward_norm_device, sag_policy_backward_norm_device: sag_policy_forward_device and sag_policy_backward_device
+ * under the unchanged descriptors; everything those define holds - the chains, the sampling, the grid rule, the limits
+ * (backward: hidden <= 128, SAG_ERR_UNSUPPORTED above), the determinism, the refusals - except that every observation element
+ * x of column k is replaced, where the row is staged, by
+ *   xh = fl(fl(x - mean[k]) * rstd[k]);   xh = xh < -clip ? -clip : xh;   xh = xh > clip ? clip : xh
+ * with no contraction, bit for bit (a NaN passes through).  d_table is [2][obs_dim] f32 as sag_obs_stats_device writes it.
+ * The zero-filled rows of a partial tile (at or beyond the last row) stay zero and are not normalised.  clip = +infinity
+ * clamps nothing.
+ * Additional refusals (SAG_ERR_ARG, nothing enqueued): d_table NULL or not 16-byte aligned; clip <= 0 or NaN. */
+int sag_policy_forward_norm_device(sag_ctx* ctx, const sag_policy_desc* desc, const float* d_table, float clip);
+int sag_policy_backward_norm_device(sag_ctx* ctx, const sag_policy_grad_desc* desc, const float* d_table, float clip);
+
 /* ---- fork on the device (throughput mode) -------------------------------------------------------
  * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`
  * itself (a fork inside a batch) or another one, of any n_envs (a few real envs feeding many planner envs; a second context

@@ -38,7 +38,8 @@ EXPORTS = [
     'sag_episode_clear', 'sag_copy_rows_device', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
     'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device',
     'sag_policy_forward_device', 'sag_policy_backward_device', 'sag_adam_device',
-    'sag_moments_device', 'sag_advantage_mix_device', 'sag_lagrange_device', 'sag_grad_clip_device'
+    'sag_moments_device', 'sag_advantage_mix_device', 'sag_lagrange_device', 'sag_grad_clip_device',
+    'sag_obs_stats_device', 'sag_policy_forward_norm_device', 'sag_policy_backward_norm_device'
 ]
 
 
@@ -114,6 +115,13 @@ class GradClipDesc(C.Structure):
       (k, C.c_void_p) for k in ('d_grad', 'd_out')]
 
 
+class ObsStatsDesc(C.Structure):
+  """sag_obs_stats_desc (include/sag.h)."""
+  _fields_ = [(k, C.c_int32) for k in ('n_rows', 'n_planes', 'pitch', 'obs_pitch', 'max_blocks', 'flags')] + [
+      ('eps', C.c_float), ('reserved', C.c_float)] + [(k, C.c_void_p) for k in ('d_obs', 'd_state', 'd_table')]
+
+
+OBS_STATS_TABLE_ONLY = 1          # enum sag_obs_stats_flags
 POLICY_RELU, POLICY_TANH = 0, 1   # enum sag_policy_activation
 ADV_RAW, ADV_CENTER, ADV_STANDARDIZE = 0, 1, 2   # enum sag_advantage_mode
 POLICY_MEAN = 1                   # enum sag_policy_flags
@@ -198,6 +206,13 @@ def load():
   lib.sag_advantage_mix_device.argtypes = [vp, C.POINTER(AdvantageMixDesc)]
   lib.sag_lagrange_device.argtypes = [vp, C.POINTER(LagrangeDesc)]
   lib.sag_grad_clip_device.argtypes = [vp, C.POINTER(GradClipDesc)]
+  # (a SAG_LIB library of the commit before lacks these three: it still loads for an A/B run of the plain paths, and a call
+  # of one of them raises AttributeError)
+  for name, sig in (('sag_obs_stats_device', [vp, C.POINTER(ObsStatsDesc)]),
+                    ('sag_policy_forward_norm_device', [vp, C.POINTER(PolicyDesc), vp, C.c_float]),
+                    ('sag_policy_backward_norm_device', [vp, C.POINTER(PolicyGradDesc), vp, C.c_float])):
+    if hasattr(lib, name):
+      getattr(lib, name).argtypes = sig
   _lib = lib
   return lib
 
@@ -580,6 +595,16 @@ class Context:
                    *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp, d_value, d_cvalue)])
     self._check(self.lib.sag_policy_forward_device(self.h, C.byref(d)), 'sag_policy_forward_device')
 
+  def policy_forward_norm(self, n_rows, hidden, d_params, d_obs, d_table, clip=10.0, logp_const=0.0, d_actions=None, d_logp=None,
+                          d_value=None, d_cvalue=None, activation=POLICY_RELU, flags=0, draw=0, row0=0, obs_pitch=None):
+    """sag_policy_forward_norm_device: policy_forward with every observation element replaced, where its row is staged, by
+    clamp((x - mean) * rstd, -clip, clip) under d_table = mean [obs_dim] then rstd [obs_dim] (what obs_stats writes)."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = PolicyDesc(int(n_rows), int(hidden), int(activation), int(flags), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), 0,
+                   int(draw) & 0xffffffff, int(row0) & 0xffffffff, float(logp_const),
+                   *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp, d_value, d_cvalue)])
+    self._check(self.lib.sag_policy_forward_norm_device(self.h, C.byref(d), ptr(d_table), float(clip)), 'sag_policy_forward_norm_device')
+
   def policy_backward(self, n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale,
                       d_cadv=None, d_cret=None, clip=0.2, vf_coef=0.5, cvf_coef=0.5, ent_coef=0.0, adv_affine=(1.0, 0.0),
                       cadv_affine=(0.0, 0.0), activation=POLICY_RELU, flags=0, max_blocks=0, obs_pitch=None):
@@ -592,6 +617,27 @@ class Context:
                        float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
                        *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
     self._check(self.lib.sag_policy_backward_device(self.h, C.byref(d)), 'sag_policy_backward_device')
+
+  def policy_backward_norm(self, n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale,
+                           d_table, obs_clip=10.0, d_cadv=None, d_cret=None, clip=0.2, vf_coef=0.5, cvf_coef=0.5, ent_coef=0.0,
+                           adv_affine=(1.0, 0.0), cadv_affine=(0.0, 0.0), activation=POLICY_RELU, flags=0, max_blocks=0, obs_pitch=None):
+    """sag_policy_backward_norm_device: policy_backward over observations normalised under d_table and clamped to
+    +-obs_clip where they are staged, as policy_forward_norm does."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = PolicyGradDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(hidden),
+                       int(activation), int(flags), int(max_blocks), float(clip), float(vf_coef), float(cvf_coef), float(ent_coef),
+                       float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
+                       *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
+    self._check(self.lib.sag_policy_backward_norm_device(self.h, C.byref(d), ptr(d_table), float(obs_clip)), 'sag_policy_backward_norm_device')
+
+  def obs_stats(self, d_state, d_table, d_obs=None, n_rows=0, n_planes=0, pitch=0, obs_pitch=None, eps=1e-8, max_blocks=0, table_only=False):
+    """sag_obs_stats_device: the per-column moments of n_planes x n_rows observation rows (planes `pitch` rows, rows obs_pitch
+    floats apart) merged into d_state = {count, mean [obs_dim], M2 [obs_dim]} float64, and d_table = mean, rstd float32 made from
+    it; table_only=True rewrites the table from the state and reads no observations.  Enqueued on the context stream."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    d = ObsStatsDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(max_blocks),
+                     OBS_STATS_TABLE_ONLY if table_only else 0, float(eps), 0.0, ptr(d_obs), ptr(d_state), ptr(d_table))
+    self._check(self.lib.sag_obs_stats_device(self.h, C.byref(d)), 'sag_obs_stats_device')
 
   def adam(self, n, d_param, d_grad, d_m, d_v, step, beta1=0.9, beta2=0.999, eps=1e-8, clamp_first=None, clamp_lo=0.0):
     """sag_adam_device: one Adam step on n float32 elements (the header has the chain; `step` is the bias-corrected learning

@@ -27,6 +27,7 @@
 #include "sag_policy.hpp"
 #include "sag_policy_grad.hpp"
 #include "sag_learner.hpp"
+#include "sag_obs_norm.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -122,6 +123,8 @@ struct sag_ctx {
   float* d_pgrad = nullptr; size_t pgrad_floats = 0;
   // sag_moments_device, sag_grad_clip_device: one (sum, count) partial per block
   float* d_lpart = nullptr; size_t lpart_blocks = 0;
+  // sag_obs_stats_device: the batch means (f64, f32), then one [obs_dim] partial per block; allocated on first use for the largest grid
+  void* d_obsn = nullptr;
   std::string err;
 };
 
@@ -581,7 +584,7 @@ int sag_destroy(sag_ctx* c) {
   for (auto& e : c->ev_pool) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
   void* bufs[] = {c->S, c->I, c->G, c->d_rows, c->d_count, c->d_kind, c->L_f, c->L_i, c->st_f, c->st_i, c->st_ids, c->d_act, c->d_noise,
                   c->d_tape, c->d_obs, c->d_rew, c->d_cost, c->d_done, c->d_met, c->d_used, c->scratch, c->d_rgb, c->d_dr, c->d_dg_sched, c->d_hot,
-                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot, c->d_palive, c->d_prank, c->d_pshift, c->d_pgrad, c->d_lpart};
+                  c->d_ext_cc, c->d_ext_btn, c->d_descs, c->d_desc_of_env, c->d_rstat, c->d_rbound, c->d_rtot, c->d_acc, c->d_ftot, c->d_palive, c->d_prank, c->d_pshift, c->d_pgrad, c->d_lpart, c->d_obsn};
   for (void* b : bufs) if (b) (void)hipFree(b);
   if (c->pin) (void)hipHostFree(c->pin);
   if (c->stream2) { (void)hipStreamSynchronize(c->stream2); (void)hipStreamDestroy(c->stream2); }
@@ -1212,26 +1215,34 @@ int sag_gae_device(sag_ctx* c, const sag_gae_desc* d) {
 }
 
 // ---- actor-critic MLP (sag_policy.hpp) ----
-int sag_policy_forward_device(sag_ctx* c, const sag_policy_desc* d) {
-  if (!c) return SAG_ERR_ARG;
-  if (!d) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: desc is NULL");
-  if (!d->d_params || !d->d_obs) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: d_params and d_obs must be given");
+namespace {
+
+// the table and clip of the _norm entry points (table == nullptr: the plain ones)
+int norm_args_ok(sag_ctx* c, const char* who, const float* d_table, float clip) {
+  if (!d_table || misaligned(d_table, 16)) return fail(c, SAG_ERR_ARG, "%s: d_table is NULL or not 16-byte aligned", who);
+  if (!(clip > 0.0f)) return fail(c, SAG_ERR_ARG, "%s: clip = %g is not above 0", who, (double)clip);
+  return 0;
+}
+
+int policy_forward(sag_ctx* c, const char* who, const sag_policy_desc* d, const float* d_table, float clip) {
+  if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
+  if (!d->d_params || !d->d_obs) return fail(c, SAG_ERR_ARG, "%s: d_params and d_obs must be given", who);
   if (misaligned(d->d_obs, 16) || misaligned(d->d_params, 4) || misaligned(d->d_actions, 4) || misaligned(d->d_logp, 4) ||
       misaligned(d->d_value, 4) || misaligned(d->d_cvalue, 4))
-    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: a misaligned buffer (d_obs 16 bytes; parameters and outputs 4)");
+    return fail(c, SAG_ERR_ARG, "%s: a misaligned buffer (d_obs 16 bytes; parameters and outputs 4)", who);
   if (d->hidden < 32 || d->hidden > 32 * POLICY_MAX_TILES || (d->hidden & 31))
-    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: hidden = %d is not a multiple of 32 in 32 ... %d", d->hidden, 32 * POLICY_MAX_TILES);
+    return fail(c, SAG_ERR_ARG, "%s: hidden = %d is not a multiple of 32 in 32 ... %d", who, d->hidden, 32 * POLICY_MAX_TILES);
   if (d->activation != SAG_POLICY_RELU && d->activation != SAG_POLICY_TANH)
-    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: activation = %d", d->activation);
-  if (d->flags & ~SAG_POLICY_MEAN) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: unknown flag bits 0x%x", d->flags & ~SAG_POLICY_MEAN);
+    return fail(c, SAG_ERR_ARG, "%s: activation = %d", who, d->activation);
+  if (d->flags & ~SAG_POLICY_MEAN) return fail(c, SAG_ERR_ARG, "%s: unknown flag bits 0x%x", who, d->flags & ~SAG_POLICY_MEAN);
   if (d->obs_pitch < c->rb.obs_dim || (d->obs_pitch & 3))
-    return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: obs_pitch = %d (rows of %d floats, a multiple of 4)", d->obs_pitch, c->rb.obs_dim);
-  if (d->n_rows < 1) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: n_rows = %d", d->n_rows);
-  if (!std::isfinite(d->logp_const)) return fail(c, SAG_ERR_ARG, "sag_policy_forward_device: logp_const is not finite");
+    return fail(c, SAG_ERR_ARG, "%s: obs_pitch = %d (rows of %d floats, a multiple of 4)", who, d->obs_pitch, c->rb.obs_dim);
+  if (d->n_rows < 1) return fail(c, SAG_ERR_ARG, "%s: n_rows = %d", who, d->n_rows);
+  if (!std::isfinite(d->logp_const)) return fail(c, SAG_ERR_ARG, "%s: logp_const is not finite", who);
   if (c->rb.obs_dim > POLICY_MAX_OBS || (c->rb.obs_dim & 3) || c->rb.nu + 2 > 16)
-    return fail(c, SAG_ERR_UNSUPPORTED, "sag_policy_forward_device: obs_dim = %d, nu = %d", c->rb.obs_dim, c->rb.nu);
+    return fail(c, SAG_ERR_UNSUPPORTED, "%s: obs_dim = %d, nu = %d", who, c->rb.obs_dim, c->rb.nu);
   HIPCHK(c, hipSetDevice(c->cfg.device));
-  PolicyArgs a;
+  PolicyNormArgs a;
   a.n_rows = d->n_rows; a.obs_dim = c->rb.obs_dim; a.nu = c->rb.nu; a.activation = d->activation;
   a.mean_only = (d->flags & SAG_POLICY_MEAN) != 0; a.obs_pitch = d->obs_pitch; a.lds_pitch = policy_lds_pitch(c->rb.obs_dim);
   const size_t lds = (size_t)POLICY_ROWS * a.lds_pitch * sizeof(float);
@@ -1239,25 +1250,54 @@ int sag_policy_forward_device(sag_ctx* c, const sag_policy_desc* d) {
   a.k0 = (uint32_t)(c->cfg.seed & 0xffffffffu); a.k1 = (uint32_t)(c->cfg.seed >> 32);
   a.logp_const = d->logp_const; a.params = d->d_params; a.obs = d->d_obs;
   a.actions = d->d_actions; a.logp = d->d_logp; a.value = d->d_value; a.cvalue = d->d_cvalue;
+  a.table = d_table; a.obs_clip = clip;
+  const PolicyArgs& plain = a;
   const dim3 grid((unsigned)(((size_t)d->n_rows + POLICY_ROWS - 1) / POLICY_ROWS)), block(WAVE);
-  switch (d->hidden / 32) {
-    case 1: hipLaunchKernelGGL((k_policy_forward<1>), grid, block, lds, c->stream, a); break;
-    case 2: hipLaunchKernelGGL((k_policy_forward<2>), grid, block, lds, c->stream, a); break;
-    case 3: hipLaunchKernelGGL((k_policy_forward<3>), grid, block, lds, c->stream, a); break;
-    case 4: hipLaunchKernelGGL((k_policy_forward<4>), grid, block, lds, c->stream, a); break;
-    case 5: hipLaunchKernelGGL((k_policy_forward<5>), grid, block, lds, c->stream, a); break;
-    case 6: hipLaunchKernelGGL((k_policy_forward<6>), grid, block, lds, c->stream, a); break;
-    case 7: hipLaunchKernelGGL((k_policy_forward<7>), grid, block, lds, c->stream, a); break;
-    default: hipLaunchKernelGGL((k_policy_forward<8>), grid, block, lds, c->stream, a); break;
+  if (!d_table) {
+    switch (d->hidden / 32) {
+      case 1: hipLaunchKernelGGL((k_policy_forward<1>), grid, block, lds, c->stream, plain); break;
+      case 2: hipLaunchKernelGGL((k_policy_forward<2>), grid, block, lds, c->stream, plain); break;
+      case 3: hipLaunchKernelGGL((k_policy_forward<3>), grid, block, lds, c->stream, plain); break;
+      case 4: hipLaunchKernelGGL((k_policy_forward<4>), grid, block, lds, c->stream, plain); break;
+      case 5: hipLaunchKernelGGL((k_policy_forward<5>), grid, block, lds, c->stream, plain); break;
+      case 6: hipLaunchKernelGGL((k_policy_forward<6>), grid, block, lds, c->stream, plain); break;
+      case 7: hipLaunchKernelGGL((k_policy_forward<7>), grid, block, lds, c->stream, plain); break;
+      default: hipLaunchKernelGGL((k_policy_forward<8>), grid, block, lds, c->stream, plain); break;
+    }
+  } else {
+    switch (d->hidden / 32) {
+      case 1: hipLaunchKernelGGL((k_policy_forward<1, true>), grid, block, lds, c->stream, a); break;
+      case 2: hipLaunchKernelGGL((k_policy_forward<2, true>), grid, block, lds, c->stream, a); break;
+      case 3: hipLaunchKernelGGL((k_policy_forward<3, true>), grid, block, lds, c->stream, a); break;
+      case 4: hipLaunchKernelGGL((k_policy_forward<4, true>), grid, block, lds, c->stream, a); break;
+      case 5: hipLaunchKernelGGL((k_policy_forward<5, true>), grid, block, lds, c->stream, a); break;
+      case 6: hipLaunchKernelGGL((k_policy_forward<6, true>), grid, block, lds, c->stream, a); break;
+      case 7: hipLaunchKernelGGL((k_policy_forward<7, true>), grid, block, lds, c->stream, a); break;
+      default: hipLaunchKernelGGL((k_policy_forward<8, true>), grid, block, lds, c->stream, a); break;
+    }
   }
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }
 
-// ---- the update (sag_policy_grad.hpp) ----
-int sag_policy_backward_device(sag_ctx* c, const sag_policy_grad_desc* d) {
+}  // namespace
+
+int sag_policy_forward_device(sag_ctx* c, const sag_policy_desc* d) {
   if (!c) return SAG_ERR_ARG;
-  const char* who = "sag_policy_backward_device";
+  return policy_forward(c, "sag_policy_forward_device", d, nullptr, 0.0f);
+}
+
+int sag_policy_forward_norm_device(sag_ctx* c, const sag_policy_desc* d, const float* d_table, float clip) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_policy_forward_norm_device";
+  if (int rc = norm_args_ok(c, who, d_table, clip)) return rc;
+  return policy_forward(c, who, d, d_table, clip);
+}
+
+// ---- the update (sag_policy_grad.hpp) ----
+namespace {
+
+int policy_backward(sag_ctx* c, const char* who, const sag_policy_grad_desc* d, const float* d_table, float obs_clip) {
   if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
   if (!d->d_params || !d->d_obs || !d->d_actions || !d->d_logp_old || !d->d_adv || !d->d_ret || !d->d_grad)
     return fail(c, SAG_ERR_ARG, "%s: d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret and d_grad must be given", who);
@@ -1282,7 +1322,7 @@ int sag_policy_backward_device(sag_ctx* c, const sag_policy_grad_desc* d) {
     return fail(c, SAG_ERR_UNSUPPORTED, "%s: hidden = %d: the backward pass is built for hidden <= %d", who, d->hidden, 32 * PGRAD_MAX_TILES);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const int od = c->rb.obs_dim, nu = c->rb.nu, H = d->hidden, NO = nu + 2;
-  PolicyGradArgs a;
+  PolicyGradNormArgs a;
   a.total = (int64_t)d->n_planes * d->n_rows;
   a.n_rows = d->n_rows; a.pitch = d->pitch; a.obs_dim = od; a.nu = nu; a.activation = d->activation; a.obs_pitch = d->obs_pitch;
   a.n_params = od * H + H + H * H + H + H * NO + NO + nu;
@@ -1290,6 +1330,7 @@ int sag_policy_backward_device(sag_ctx* c, const sag_policy_grad_desc* d) {
   a.adv_mul = d->adv_mul; a.adv_sub = d->adv_sub; a.cadv_mul = d->cadv_mul; a.cadv_sub = d->cadv_sub;
   a.params = d->d_params; a.obs = d->d_obs; a.actions = d->d_actions; a.logp_old = d->d_logp_old; a.adv = d->d_adv; a.ret = d->d_ret;
   a.cadv = d->d_cadv; a.cret = d->d_cret;
+  a.table = d_table; a.obs_clip = obs_clip;
   const int grid = pgrad_grid(a.total, d->max_blocks), words = a.n_params + PGRAD_STATS;
   const size_t need = (size_t)grid * words;
   if (c->pgrad_floats < need) {   // (a workspace in use by the stream is not freed under it)
@@ -1299,19 +1340,43 @@ int sag_policy_backward_device(sag_ctx* c, const sag_policy_grad_desc* d) {
     c->pgrad_floats = need;
   }
   a.part = c->d_pgrad;
+  const PolicyGradArgs& plain = a;
   const size_t lds = pgrad_lds_floats(od, H) * sizeof(float);
   const dim3 g((unsigned)grid), block(PGRAD_THREADS);
-  switch (H / 32) {
-    case 1: hipLaunchKernelGGL((k_policy_backward<1>), g, block, lds, c->stream, a); break;
-    case 2: hipLaunchKernelGGL((k_policy_backward<2>), g, block, lds, c->stream, a); break;
-    case 3: hipLaunchKernelGGL((k_policy_backward<3>), g, block, lds, c->stream, a); break;
-    default: hipLaunchKernelGGL((k_policy_backward<4>), g, block, lds, c->stream, a); break;
+  if (!d_table) {
+    switch (H / 32) {
+      case 1: hipLaunchKernelGGL((k_policy_backward<1>), g, block, lds, c->stream, plain); break;
+      case 2: hipLaunchKernelGGL((k_policy_backward<2>), g, block, lds, c->stream, plain); break;
+      case 3: hipLaunchKernelGGL((k_policy_backward<3>), g, block, lds, c->stream, plain); break;
+      default: hipLaunchKernelGGL((k_policy_backward<4>), g, block, lds, c->stream, plain); break;
+    }
+  } else {
+    switch (H / 32) {
+      case 1: hipLaunchKernelGGL((k_policy_backward<1, true>), g, block, lds, c->stream, a); break;
+      case 2: hipLaunchKernelGGL((k_policy_backward<2, true>), g, block, lds, c->stream, a); break;
+      case 3: hipLaunchKernelGGL((k_policy_backward<3, true>), g, block, lds, c->stream, a); break;
+      default: hipLaunchKernelGGL((k_policy_backward<4, true>), g, block, lds, c->stream, a); break;
+    }
   }
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_policy_grad_reduce, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, c->d_pgrad, grid, words, d->scale,
                      (d->flags & SAG_POLICY_GRAD_ACCUMULATE) != 0, d->d_grad);
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
+}
+
+}  // namespace
+
+int sag_policy_backward_device(sag_ctx* c, const sag_policy_grad_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  return policy_backward(c, "sag_policy_backward_device", d, nullptr, 0.0f);
+}
+
+int sag_policy_backward_norm_device(sag_ctx* c, const sag_policy_grad_desc* d, const float* d_table, float clip) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_policy_backward_norm_device";
+  if (int rc = norm_args_ok(c, who, d_table, clip)) return rc;
+  return policy_backward(c, who, d, d_table, clip);
 }
 
 int sag_adam_device(sag_ctx* c, const sag_adam_desc* d) {
@@ -1451,6 +1516,56 @@ int sag_grad_clip_device(sag_ctx* c, const sag_grad_clip_desc* d) {
   hipLaunchKernelGGL((k_learn_partial<2>), g, block, 0, c->stream, a);
   HIPCHK(c, hipGetLastError());
   hipLaunchKernelGGL(k_grad_clip_scale, g, block, 0, c->stream, a.part_sum, grid, d->max_norm, (uint32_t)d->n, d->d_grad, d->d_out);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
+}
+
+// ---- observation statistics and the table (sag_obs_norm.hpp) ----
+int sag_obs_stats_device(sag_ctx* c, const sag_obs_stats_desc* d) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_obs_stats_device";
+  if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
+  if (d->flags & ~SAG_OBS_STATS_TABLE_ONLY) return fail(c, SAG_ERR_ARG, "%s: unknown flag bits 0x%x", who, d->flags & ~SAG_OBS_STATS_TABLE_ONLY);
+  const bool table_only = (d->flags & SAG_OBS_STATS_TABLE_ONLY) != 0;
+  if (!d->d_state || !d->d_table) return fail(c, SAG_ERR_ARG, "%s: d_state and d_table must be given", who);
+  if (misaligned(d->d_state, 8) || misaligned(d->d_table, 16)) return fail(c, SAG_ERR_ARG, "%s: d_state is not 8-byte or d_table not 16-byte aligned", who);
+  if (!std::isfinite(d->eps) || !(d->eps > 0.0f)) return fail(c, SAG_ERR_ARG, "%s: eps = %g", who, (double)d->eps);
+  const int od = c->rb.obs_dim;
+  if (!table_only) {
+    if (!d->d_obs) return fail(c, SAG_ERR_ARG, "%s: d_obs is NULL without SAG_OBS_STATS_TABLE_ONLY", who);
+    if (misaligned(d->d_obs, 16)) return fail(c, SAG_ERR_ARG, "%s: d_obs is not 16-byte aligned", who);
+    if (!span_ok(d->n_rows, d->n_planes, d->pitch))
+      return fail(c, SAG_ERR_ARG, "%s: n_rows = %d, n_planes = %d, pitch = %d (n_planes * n_rows below 2^31)", who, d->n_rows, d->n_planes, d->pitch);
+    if (d->obs_pitch < od || (d->obs_pitch & 3))
+      return fail(c, SAG_ERR_ARG, "%s: obs_pitch = %d (rows of %d floats, a multiple of 4)", who, d->obs_pitch, od);
+    if (d->max_blocks < 0) return fail(c, SAG_ERR_ARG, "%s: max_blocks = %d", who, d->max_blocks);
+  }
+  if (od > OBSN_MAX_OBS || (od & 3)) return fail(c, SAG_ERR_UNSUPPORTED, "%s: obs_dim = %d", who, od);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  if (!c->d_obsn) HIPCHK(c, hipMalloc(&c->d_obsn, obsn_ws_bytes(OBSN_MAX_BLOCKS, OBSN_MAX_OBS)));
+  double* ws_mean = static_cast<double*>(c->d_obsn);
+  float* ws_shift = reinterpret_cast<float*>(ws_mean + OBSN_MAX_OBS);
+  float* ws_part = ws_shift + OBSN_MAX_OBS;
+  ObsMergeArgs m;
+  m.n_blocks = 0; m.obs_dim = od; m.table_only = table_only; m.eps = d->eps; m.n_b = 0.0;
+  m.part = ws_part; m.mean_b = ws_mean; m.shift = ws_shift; m.state = d->d_state; m.table = d->d_table;
+  const dim3 block(OBSN_THREADS);
+  if (!table_only) {
+    const int64_t total = (int64_t)d->n_planes * d->n_rows;
+    const int grid = obsn_grid(total, d->max_blocks);
+    ObsStatsArgs a;
+    a.total = (uint32_t)total; a.n_rows = (uint32_t)d->n_rows; a.pitch = (uint32_t)d->pitch; a.obs_pitch = (uint32_t)d->obs_pitch;
+    a.obs_dim = od; a.obs = d->d_obs; a.shift = ws_shift; a.part = ws_part;
+    m.n_blocks = grid; m.n_b = (double)total;
+    const dim3 g((unsigned)grid);
+    hipLaunchKernelGGL((k_obs_partial<0>), g, block, 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(k_obs_mean, dim3(1), block, 0, c->stream, ws_part, grid, od, m.n_b, ws_mean, ws_shift);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL((k_obs_partial<1>), g, block, 0, c->stream, a);
+    HIPCHK(c, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_obs_merge, dim3(1), block, 0, c->stream, m);
   HIPCHK(c, hipGetLastError());
   return SAG_OK;
 }

@@ -2,6 +2,8 @@
 // actor-critic MLP (sag_policy_forward_device; include/sag.h defines the arithmetic).
 //   k_policy_forward<NT>   obs [n_rows][obs_dim] -> hidden -> hidden -> nu + 2 outputs (action mean, value, cost value),
 //                          hidden = 32 * NT; sampling and log-probability in the same launch; no activation leaves the CU
+//   k_policy_forward<NT, true>   the same with every observation element normalised and clamped where its row is staged
+//                          (sag_policy_forward_norm_device; sag_obs_norm.hpp has the arithmetic)
 // One wavefront per 32 rows.  Every product runs on the fp32-input MFMA (v_mfma_f32_32x32x2_f32: D = A[32][2] * B[2][32] + C,
 // bit for bit fma(a1, b1, fma(a0, b0, c)), one rounding per product), in the orientation D^T = W^T * X^T: the weights are the
 // A operand (lane l: unit row l & 31, k = l >> 5), the activations the B operand (lane l: row l & 31, k = l >> 5).  A result
@@ -16,6 +18,7 @@
 // needs the even or the odd elements of its own row; weights are read from global memory (L2) as one dword per lane and MFMA.
 #pragma once
 #include "sag_device.hpp"
+#include "sag_obs_norm.hpp"
 
 namespace sag {
 
@@ -62,6 +65,11 @@ struct PolicyArgs {
   const float* obs;
   float* actions; float* logp; float* value; float* cvalue;
 };
+// sag_policy_forward_norm_device: the same, with every staged observation element normalised under `table`
+struct PolicyNormArgs : PolicyArgs {
+  const float* table;   // mean [obs_dim], rstd [obs_dim]
+  float obs_clip;
+};
 
 // the hidden unit (0 ... 31, inside its block of 32) that sits in tile row rho: the position of rho in 0, 4, 1, 5, ...
 __device__ inline int policy_tile_unit(int rho) { return 2 * ((rho & 3) + 4 * (rho >> 3)) + ((rho >> 2) & 1); }
@@ -74,8 +82,12 @@ __device__ inline float policy_act(float x, int activation) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
 }
 
-template <int NT>
-__global__ __launch_bounds__(WAVE) void k_policy_forward(PolicyArgs p) {
+template <bool NORM> struct PolicyArgsOf { typedef PolicyArgs type; };
+template <> struct PolicyArgsOf<true> { typedef PolicyNormArgs type; };
+
+// NORM: sag_policy_forward_norm_device; the plain instances are what they were before the switch existed
+template <int NT, bool NORM = false>
+__global__ __launch_bounds__(WAVE) void k_policy_forward(typename PolicyArgsOf<NORM>::type p) {
 #pragma clang fp contract(off)
   constexpr int H = 32 * NT;
   HIP_DYNAMIC_SHARED(float4, tile4)   // POLICY_ROWS * lds_pitch floats: sized for the robot, so that LDS does not bound the occupancy
@@ -87,7 +99,10 @@ __global__ __launch_bounds__(WAVE) void k_policy_forward(PolicyArgs p) {
   for (int piece = lane; piece < POLICY_ROWS * Q; piece += WAVE) {
     const int r = piece / Q, q = piece - r * Q;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);   // rows at or beyond n_rows are not read
-    if (row0 + (size_t)r < (size_t)p.n_rows) v = *reinterpret_cast<const float4*>(p.obs + (row0 + (size_t)r) * (size_t)p.obs_pitch + 4 * q);
+    if (row0 + (size_t)r < (size_t)p.n_rows) {
+      v = *reinterpret_cast<const float4*>(p.obs + (row0 + (size_t)r) * (size_t)p.obs_pitch + 4 * q);
+      if constexpr (NORM) v = obs_norm_piece(v, p.table, od, q, p.obs_clip);
+    }
     *reinterpret_cast<float4*>(tile + r * LP + 4 * q) = v;
   }
   __syncthreads();

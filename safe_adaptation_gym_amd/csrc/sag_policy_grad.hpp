@@ -1,6 +1,8 @@
 // sag_policy_grad.hpp - the learner's update on the context stream (include/sag.h defines both functions):
 //   k_policy_backward<NT>   the gradient of the PPO-Lagrangian loss through the MLP of sag_policy.hpp, hidden = 32 * NT <= 128:
 //                           persistent blocks of four wavefronts, one partial [n_params + 8] per block, no atomics
+//                           (k_policy_backward<NT, true>: over observations normalised where they are staged,
+//                           sag_policy_backward_norm_device)
 //   k_policy_grad_reduce    the partials summed in ascending block order into d_grad
 //   k_adam                  the elementwise optimiser step
 // Per tile of 32 rows a block keeps four images in LDS, all [row][unit] at a pitch of 4 (mod 32) floats: X (the staged
@@ -47,6 +49,11 @@ struct PolicyGradArgs {
   const float* obs; const float* actions; const float* logp_old; const float* adv; const float* ret;
   const float* cadv; const float* cret;
   float* part;   // [gridDim.x][n_params + 8]
+};
+// sag_policy_backward_norm_device: the same, with every staged observation element normalised under `table`
+struct PolicyGradNormArgs : PolicyGradArgs {
+  const float* table;   // mean [obs_dim], rstd [obs_dim]
+  float obs_clip;
 };
 
 // Between two output tiles the compiler must not hoist the next tile's 32 LDS reads above this tile's MFMAs: with nine tiles
@@ -127,8 +134,12 @@ __device__ inline void pgrad_put_tile(float* out, int ld, int K, int J, int ki, 
   }
 }
 
-template <int NT>
-__global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(PolicyGradArgs p) {
+template <bool NORM> struct PolicyGradArgsOf { typedef PolicyGradArgs type; };
+template <> struct PolicyGradArgsOf<true> { typedef PolicyGradNormArgs type; };
+
+// NORM: sag_policy_backward_norm_device; the plain instances are what they were before the switch existed
+template <int NT, bool NORM = false>
+__global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(typename PolicyGradArgsOf<NORM>::type p) {
 #pragma clang fp contract(off)
   constexpr int H = 32 * NT, PH = H + 4, PD = PGRAD_DO_PITCH;
   constexpr int T3 = (NT + PGRAD_WAVES - 1) / PGRAD_WAVES, T2 = (NT * NT + PGRAD_WAVES - 1) / PGRAD_WAVES, T1 = NT;   // tiles per wavefront
@@ -195,6 +206,7 @@ __global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(PolicyGradArg
         const int64_t plane = g / p.n_rows;
         const int64_t src = plane * p.pitch + (g - plane * p.n_rows);
         v = *reinterpret_cast<const float4*>(p.obs + (size_t)src * (size_t)p.obs_pitch + 4 * q);
+        if constexpr (NORM) v = obs_norm_piece(v, p.table, od, q, p.obs_clip);
       }
       *reinterpret_cast<float4*>(X + r * PX + 4 * q) = v;
     }

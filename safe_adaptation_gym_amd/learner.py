@@ -24,7 +24,8 @@ MOMENTS_EPS = 1e-8
 class PPOLearner:
   """learner = PPOLearner(pi, buf, lr=3e-4, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5, cost_vf_coef=0.5, ent_coef=0.0,
                           cost_weight=0.0, betas=(0.9, 0.999), eps=1e-8, std_min=1e-3, normalize_advantage=False,
-                          cost_advantage='center', max_grad_norm=None, cost_budget=None, lagrange_lr=0.05, lagrange_max=inf)
+                          cost_advantage='center', max_grad_norm=None, cost_budget=None, lagrange_lr=0.05, lagrange_max=inf,
+                          update_obs_stats=True)
 
   pi: an MLPPolicy (hidden <= 128), buf: a RolloutBuffer of the same env.  The learner owns the Adam moments and the step count.
 
@@ -47,11 +48,19 @@ class PPOLearner:
                                none ended.  Statistics: cost_weight (the value this update used), episode_cost, episodes.
                                The constructor's cost_weight is the initial value; learner.cost_weight reads the value cached
                                at the last join, and assigning to it uploads.
-  Without cost_budget, cost_weight is a plain attribute and stays what it was set to."""
+  Without cost_budget, cost_weight is a plain attribute and stays what it was set to.
+
+  A policy built with normalize_observations=True normalises inside its backward pass (sag_policy_backward_norm_device), and
+  update() enqueues pi.update_obs_stats(buf) once, after the last round and ahead of pi.refresh(): collect, evaluate and every
+  epoch of one update see one table - so buf.logp and the first epoch's ratio agree - and the next collect sees statistics
+  that include this batch.  Still one host join per update.  The very first collect runs under the identity table unless
+  pi.update_obs_stats() was called on a warm-up rollout.  update_obs_stats=False turns the hook off; so does
+  pi.obs_norm_frozen.  With a policy that does not normalise, update() enqueues what it did before."""
 
   def __init__(self, pi, buf, lr=3e-4, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5, cost_vf_coef=0.5, ent_coef=0.0,
                cost_weight=0.0, betas=(0.9, 0.999), eps=1e-8, std_min=1e-3, normalize_advantage=False, cost_advantage='center',
-               max_grad_norm=None, cost_budget=None, lagrange_lr=0.05, lagrange_max=float('inf')):
+               max_grad_norm=None, cost_budget=None, lagrange_lr=0.05, lagrange_max=float('inf'), update_obs_stats=True):
+    self.update_obs_stats = bool(update_obs_stats)
     if buf.env is not pi.env:
       raise ValueError('PPOLearner: the policy and the buffer belong to different envs')
     if pi.hidden > 128:
@@ -167,6 +176,8 @@ class PPOLearner:
         self.t += 1
         c.adam(pi.n_params, pi._buf, pi._gbuf, self._m, self._v, self.step_size(self.t), beta1=b1, beta2=b2, eps=self.eps,
                clamp_first=pi.n_params - pi.nu, clamp_lo=self.std_min)
+    if self.update_obs_stats and pi.normalize_observations and not pi.obs_norm_frozen:
+      pi.update_obs_stats(buf)   # after the last round: collect, evaluate and every epoch of this update saw one table
     pi.refresh()   # joins the stream: the parameters and the statistics below are complete
     s = pi.grad['stats'].numpy()
     rows = s[5] if s[5] > 0 else 1.0

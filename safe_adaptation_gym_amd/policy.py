@@ -43,9 +43,20 @@ class MLPPolicy:
   grad: {the keys of `params`, 'stats' [8]} - DeviceArray views of ONE buffer of n_params + 8 floats that backward() fills
   (sag_policy_backward_device) and an optimiser reads in place (PPOLearner; Context.adam).
 
-  Every method but set_params / get_params / refresh / evaluate only enqueues work: no wait, no host copy."""
+  normalize_observations=True: the policy owns running per-column moments of the observations (float64 {count, mean, M2}) and
+  the float32 table made from them (mean, 1 / sqrt(var + obs_eps)) on the device, and forward / backward - hence act_into,
+  evaluate, __call__ and PPOLearner - read every observation element as clamp((x - mean) * rstd, -obs_clip, obs_clip), applied
+  where the kernels stage the row (sag_policy_forward_norm_device, sag_policy_backward_norm_device): no normalised copy of the
+  observations is written.  The moments start empty, which is the identity table; update_obs_stats(buf) folds a rollout in
+  (PPOLearner.update() does so once per update, after its last round).  So the first collect runs under the identity table
+  unless update_obs_stats is called on a warm-up rollout first.  get_obs_norm() / set_obs_norm() carry the state through a
+  checkpoint; obs_norm_frozen = True stops the statistics (evaluation).  With the switch off none of this exists and
+  update_obs_stats / get_obs_norm / set_obs_norm raise ValueError.
 
-  def __init__(self, env, hidden=64, activation='relu', seed=0, log_std=-0.5):
+  Every method but set_params / get_params / refresh / evaluate / get_obs_norm / set_obs_norm only enqueues work: no wait, no
+  host copy."""
+
+  def __init__(self, env, hidden=64, activation='relu', seed=0, log_std=-0.5, normalize_observations=False, obs_clip=10.0, obs_eps=1e-8):
     from safe_adaptation_gym_amd.envs import BatchedSafeAdaptationGym
     if not isinstance(env, BatchedSafeAdaptationGym):
       raise ValueError('MLPPolicy: env must be a BatchedSafeAdaptationGym')
@@ -60,6 +71,11 @@ class MLPPolicy:
       raise ValueError(f'MLPPolicy: activation={activation!r}: one of {sorted(ACTIVATIONS)}')
     if not np.isfinite(log_std):
       raise ValueError(f'MLPPolicy: log_std={log_std}')
+    if normalize_observations and (not obs_clip > 0 or not (np.isfinite(obs_eps) and obs_eps > 0)):
+      raise ValueError(f'MLPPolicy: obs_clip={obs_clip}, obs_eps={obs_eps}')
+    self.normalize_observations, self.obs_clip, self.obs_eps = bool(normalize_observations), float(obs_clip), float(obs_eps)
+    self.obs_norm_frozen = False
+    self._obs_state = self._obs_table = None
     self.env, self.hidden, self.activation = env, H, activation
     self.obs_dim, self.nu = od, nu = env.robot.obs_dim, env.robot.nu
     self._ctx = c = env._ctx[0]
@@ -84,6 +100,9 @@ class MLPPolicy:
       init[k] = rng.uniform(-bound, bound, self.shapes[k]).astype(np.float32)
     init['std'] = np.full(nu, np.exp(log_std), np.float32)
     self.set_params(init)
+    if self.normalize_observations:
+      self._obs_state, self._obs_table = c.dev_alloc((1 + 2 * od) * 8), c.dev_alloc(2 * od * 4)
+      self.set_obs_norm(0.0, np.zeros(od), np.zeros(od))   # the empty state: the identity table
 
   # -- parameters ------------------------------------------------------------------------------------------------------
   def set_params(self, params):
@@ -159,11 +178,14 @@ class MLPPolicy:
     if rows < 1:
       return
     sampled = actions is not None and not deterministic
-    self._ctx.policy_forward(rows, self.hidden, self._buf, ptr, self.logp_const,
-                             d_actions=self._out(actions, (rows, self.nu), 'actions'), d_logp=self._out(logp, (rows,), 'logp'),
-                             d_value=self._out(value, (rows,), 'value'), d_cvalue=self._out(cost_value, (rows,), 'cost_value'),
-                             activation=ACTIVATIONS[self.activation], flags=0 if sampled or actions is None else nat.POLICY_MEAN,
-                             draw=self.draw, row0=row0, obs_pitch=pitch)
+    kw = dict(logp_const=self.logp_const, d_actions=self._out(actions, (rows, self.nu), 'actions'), d_logp=self._out(logp, (rows,), 'logp'),
+              d_value=self._out(value, (rows,), 'value'), d_cvalue=self._out(cost_value, (rows,), 'cost_value'),
+              activation=ACTIVATIONS[self.activation], flags=0 if sampled or actions is None else nat.POLICY_MEAN,
+              draw=self.draw, row0=row0, obs_pitch=pitch)
+    if self.normalize_observations:
+      self._ctx.policy_forward_norm(rows, self.hidden, self._buf, ptr, self._obs_table, self.obs_clip, **kw)
+    else:
+      self._ctx.policy_forward(rows, self.hidden, self._buf, ptr, **kw)
     if sampled:
       self.draw = (self.draw + 1) & 0xffffffff
 
@@ -236,18 +258,64 @@ class MLPPolicy:
     if ptr['obs'] % 16:
       raise ValueError('MLPPolicy.backward: observation rows must be 16-byte aligned')
     planes, rows, pitch = geom
-    self._ctx.policy_backward(rows, planes, pitch, self.hidden, self._buf, ptr['obs'], ptr['actions'], ptr['logp_old'], ptr['adv'],
-                              ptr['ret'], self._gbuf, scale, d_cadv=ptr['cadv'], d_cret=ptr['cret'], clip=clip, vf_coef=vf_coef,
-                              cvf_coef=cost_vf_coef, ent_coef=ent_coef, adv_affine=adv_affine, cadv_affine=cadv_affine,
-                              activation=ACTIVATIONS[self.activation], flags=nat.POLICY_GRAD_ACCUMULATE if accumulate else 0)
+    args = (rows, planes, pitch, self.hidden, self._buf, ptr['obs'], ptr['actions'], ptr['logp_old'], ptr['adv'], ptr['ret'], self._gbuf, scale)
+    kw = dict(d_cadv=ptr['cadv'], d_cret=ptr['cret'], clip=clip, vf_coef=vf_coef, cvf_coef=cost_vf_coef, ent_coef=ent_coef,
+              adv_affine=adv_affine, cadv_affine=cadv_affine, activation=ACTIVATIONS[self.activation],
+              flags=nat.POLICY_GRAD_ACCUMULATE if accumulate else 0)
+    if self.normalize_observations:
+      self._ctx.policy_backward_norm(*args, self._obs_table, self.obs_clip, **kw)
+    else:
+      self._ctx.policy_backward(*args, **kw)
+
+  # -- observation normalisation -----------------------------------------------------------------------------------------
+  def _need_norm(self, who):
+    if not self.normalize_observations:
+      raise ValueError(f'MLPPolicy.{who}: the policy was built without normalize_observations=True')
+
+  def update_obs_stats(self, rows):
+    """Folds observation rows into the running moments and rewrites the table (sag_obs_stats_device), enqueued on the stream.
+    `rows`: a RolloutBuffer - its stored steps buf.obs[0:T], without the row of the last observation - or any time-major
+    float32 device view [planes, rows, obs_dim].  Does nothing while obs_norm_frozen is set."""
+    self._need_norm('update_obs_stats')
+    if self.obs_norm_frozen:
+      return
+    obs = plane_range(rows.obs, 0, rows.T) if hasattr(rows, 'obs') and hasattr(rows, 'T') else rows
+    ptr, planes, n, pitch = self._planes(obs, (self.obs_dim,), 'obs')
+    if ptr % 16:
+      raise ValueError('MLPPolicy.update_obs_stats: observation rows must be 16-byte aligned')
+    self._ctx.obs_stats(self._obs_state, self._obs_table, ptr, n, planes, pitch, eps=self.obs_eps)
+
+  def get_obs_norm(self):
+    """-> {'count': float, 'mean': [obs_dim], 'var': [obs_dim]} as float64 NumPy (var = M2 / count, the population variance; zeros
+    while the state is empty).  Joins the stream."""
+    self._need_norm('get_obs_norm')
+    self._ctx.wait()
+    od = self.obs_dim
+    s = self._ctx.dev_download(self._obs_state, (1 + 2 * od,), np.float64)
+    n = float(s[0])
+    return {'count': n, 'mean': s[1:1 + od].copy(), 'var': s[1 + od:] / n if n > 0 else np.zeros(od)}
+
+  def set_obs_norm(self, count, mean=None, var=None):
+    """Uploads a state - set_obs_norm(count, mean, var) or set_obs_norm(the dict of get_obs_norm()) - and rewrites the table from
+    it on the device (SAG_OBS_STATS_TABLE_ONLY), so that a restored table comes from the same arithmetic as a running one."""
+    self._need_norm('set_obs_norm')
+    if isinstance(count, dict):
+      count, mean, var = count['count'], count['mean'], count['var']
+    od = self.obs_dim
+    n, mean, var = float(count), np.asarray(mean, np.float64), np.asarray(var, np.float64)
+    if mean.shape != (od,) or var.shape != (od,) or not n >= 0 or not np.isfinite(mean).all() or not (np.isfinite(var).all() and (var >= 0).all()):
+      raise ValueError(f'MLPPolicy.set_obs_norm: count >= 0, mean and var >= 0 of shape ({od},), all finite')
+    self._ctx.dev_upload(self._obs_state, np.concatenate([[n], mean, var * n]))
+    self._ctx.obs_stats(self._obs_state, self._obs_table, eps=self.obs_eps, table_only=True)
 
   def close(self):
     c = getattr(self, '_ctx', None)
     if c is not None and c.h and getattr(self, '_buf', None) is not None:
       c.dev_free(self._buf)
-      if getattr(self, '_gbuf', None) is not None:
-        c.dev_free(self._gbuf)
-    self._buf = self._gbuf = None
+      for p in (getattr(self, '_gbuf', None), getattr(self, '_obs_state', None), getattr(self, '_obs_table', None)):
+        if p is not None:
+          c.dev_free(p)
+    self._buf = self._gbuf = self._obs_state = self._obs_table = None
     self._ctx = None
 
   def __del__(self):
