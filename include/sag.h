@@ -847,6 +847,50 @@ int sag_obs_stats_device(sag_ctx* ctx, const sag_obs_stats_desc* desc);
 int sag_policy_forward_norm_device(sag_ctx* ctx, const sag_policy_desc* desc, const float* d_table, float clip);
 int sag_policy_backward_norm_device(sag_ctx* ctx, const sag_policy_grad_desc* desc, const float* d_table, float clip);
 
+/* ---- shuffled-row minibatches on the context stream (throughput mode) ------------------------------
+ * A random permutation written on the device and the backward pass over a list of rows: what a learner needs to draw every
+ * epoch's minibatches from a fresh shuffle of all T x N stored rows without an upload, a sort or a gathered copy of the batch.
+ * Both are enqueued on the context stream and return without waiting; neither copies to the host, records timing events or
+ * needs an installed layout (sag_policy_backward_rows_device shares sag_policy_backward_device's workspace and its one
+ * exception).  No atomics.
+ *
+ * sag_permutation_device: d_index[i] = pi(i) for 0 <= i < n, one 4-byte store per element; nothing at or behind d_index + n is
+ * touched.  pi is a bijection of [0, n) defined bit for bit - the same key (sag_set_seed), draw and n give the same array on
+ * every call and device:
+ *   b = max(2, bit length of (n - 1)); the walk domain is 2^b, so n <= 2^b and, for n > 2, 2^b < 2 n.
+ *   F is an unbalanced Feistel network of 6 rounds on b-bit words: wl = b / 2 (floor), wr = b - wl, L = x >> wr,
+ *   R = x & (2^wr - 1); round r = 0 ... 5:
+ *     f = word 0 of Philox4x32-10(counter = {R, draw, r, 0x18000000}, the context key) & (2^wl - 1)
+ *     (L, R) <- (R, L ^ f), then wl and wr change places
+ *   F(x) = (L << wr) | R with the widths as they stand after the last round (six is even: the starting ones).  Counter word 3
+ *   is stream 6, placed where streams 4 (0x10000000, the planner) and 5 (0x14000000, the policy) sit.
+ *   Cycle walking: x = i; do x = F(x) while x >= n; pi(i) = x.  The walk ends because F permutes [0, 2^b).
+ * pi is a keyed pseudo-random permutation, not a uniform draw from all n! orders.  Below about 16 elements the halves are 1 to
+ * 2 bits wide and the distribution over the draws is visibly non-uniform (n = 5: chi^2 / dof of the position x value table
+ * 7 to 9, where n = 130 gives 1.0 within its noise): at those sizes the function promises a bijection and nothing more.  The caller advances
+ * `draw` from call to call.
+ * SAG_ERR_ARG with nothing enqueued: a NULL ctx or d_index; d_index not 4-byte aligned; n < 1. */
+int sag_permutation_device(sag_ctx* ctx, int32_t n, uint32_t draw, int32_t* d_index);
+
+/* sag_policy_backward_rows_device: sag_policy_backward_device over a list of rows.  `desc` describes the planes exactly as
+ * there; batch row j (0 <= j < n_index) is logical element e = d_rows[j] of those planes - row e % n_rows of plane
+ * e / n_rows - read in place: no gathered copy is written.  With d_table == NULL the rows are read raw and obs_clip is ignored;
+ * otherwise they are normalised where they are staged, as sag_policy_backward_norm_device does.
+ *   d_rows  [n_index] DEVICE int32, 4-byte aligned, complete before the call in stream order (sag_permutation_device on the
+ *           same stream writes such a list; a slice d_index + a of it is a minibatch).  An entry outside
+ *           [0, n_planes * n_rows) is a row that is absent: nothing is read for it, it adds nothing to the gradient or the
+ *           statistics, and statistic 5 (the rows that took part) does not count it - a wrong list cannot read outside the
+ *           arrays.  Duplicates are allowed and count once each.
+ * The grid and tiling rule is sag_policy_backward_device's with n_index in the place of n_planes * n_rows: tiles are 32
+ * consecutive list entries, taken by the persistent blocks in the same order and followed by the same reduce.  Consequently
+ * the list 0, 1, ..., n_planes * n_rows - 1 gives the bits of sag_policy_backward_device (with a table: of
+ * sag_policy_backward_norm_device) under the same desc.  `scale` is the caller's - 1 / n_index for a minibatch's mean.
+ * SAG_ERR_ARG with nothing enqueued: everything the contiguous calls refuse; a NULL d_rows or one not 4-byte aligned;
+ * n_index < 1; with a table: d_table not 16-byte aligned, obs_clip not finite or not above 0.  SAG_ERR_UNSUPPORTED: hidden
+ * 160 ... 256, as there. */
+int sag_policy_backward_rows_device(sag_ctx* ctx, const sag_policy_grad_desc* desc, const int32_t* d_rows, int32_t n_index,
+                                    const float* d_table, float obs_clip);
+
 /* ---- fork on the device (throughput mode) -------------------------------------------------------
  * sag_fork_device: env i of `dst` takes the complete state of env d_src[i] of `src`, a context on the same device - `dst`
  * itself (a fork inside a batch) or another one, of any n_envs (a few real envs feeding many planner envs; a second context

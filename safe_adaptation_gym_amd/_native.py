@@ -39,7 +39,8 @@ EXPORTS = [
     'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device',
     'sag_policy_forward_device', 'sag_policy_backward_device', 'sag_adam_device',
     'sag_moments_device', 'sag_advantage_mix_device', 'sag_lagrange_device', 'sag_grad_clip_device',
-    'sag_obs_stats_device', 'sag_policy_forward_norm_device', 'sag_policy_backward_norm_device'
+    'sag_obs_stats_device', 'sag_policy_forward_norm_device', 'sag_policy_backward_norm_device',
+    'sag_permutation_device', 'sag_policy_backward_rows_device'
 ]
 
 
@@ -206,11 +207,13 @@ def load():
   lib.sag_advantage_mix_device.argtypes = [vp, C.POINTER(AdvantageMixDesc)]
   lib.sag_lagrange_device.argtypes = [vp, C.POINTER(LagrangeDesc)]
   lib.sag_grad_clip_device.argtypes = [vp, C.POINTER(GradClipDesc)]
-  # (a SAG_LIB library of the commit before lacks these three: it still loads for an A/B run of the plain paths, and a call
+  # (a SAG_LIB library of an earlier commit lacks some of these: it still loads for an A/B run of the plain paths, and a call
   # of one of them raises AttributeError)
   for name, sig in (('sag_obs_stats_device', [vp, C.POINTER(ObsStatsDesc)]),
                     ('sag_policy_forward_norm_device', [vp, C.POINTER(PolicyDesc), vp, C.c_float]),
-                    ('sag_policy_backward_norm_device', [vp, C.POINTER(PolicyGradDesc), vp, C.c_float])):
+                    ('sag_policy_backward_norm_device', [vp, C.POINTER(PolicyGradDesc), vp, C.c_float]),
+                    ('sag_permutation_device', [vp, C.c_int32, C.c_uint32, vp]),
+                    ('sag_policy_backward_rows_device', [vp, C.POINTER(PolicyGradDesc), vp, C.c_int32, vp, C.c_float])):
     if hasattr(lib, name):
       getattr(lib, name).argtypes = sig
   _lib = lib
@@ -607,28 +610,46 @@ class Context:
 
   def policy_backward(self, n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale,
                       d_cadv=None, d_cret=None, clip=0.2, vf_coef=0.5, cvf_coef=0.5, ent_coef=0.0, adv_affine=(1.0, 0.0),
-                      cadv_affine=(0.0, 0.0), activation=POLICY_RELU, flags=0, max_blocks=0, obs_pitch=None):
+                      cadv_affine=(0.0, 0.0), activation=POLICY_RELU, flags=0, max_blocks=0, obs_pitch=None, rows=None):
     """sag_policy_backward_device: the PPO-Lagrangian gradient and 8 statistics of n_planes x n_rows stored rows (planes `pitch`
     rows apart) into d_grad [n_params + 8], enqueued on the context stream - no wait, no host copy.  The header defines the
-    function; adv_affine = (adv_mul, adv_sub), cadv_affine likewise.  Pointers are c_void_p, ints or None."""
+    function; adv_affine = (adv_mul, adv_sub), cadv_affine likewise.  Pointers are c_void_p, ints or None.
+    rows=(d_rows, n_index): sag_policy_backward_rows_device - the batch is the n_index logical elements that the device int32
+    list at d_rows names, gathered in place."""
     ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
     d = PolicyGradDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(hidden),
                        int(activation), int(flags), int(max_blocks), float(clip), float(vf_coef), float(cvf_coef), float(ent_coef),
                        float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
                        *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
+    if rows is not None:
+      self._check(self.lib.sag_policy_backward_rows_device(self.h, C.byref(d), ptr(rows[0]), int(rows[1]), None, 0.0),
+                  'sag_policy_backward_rows_device')
+      return
     self._check(self.lib.sag_policy_backward_device(self.h, C.byref(d)), 'sag_policy_backward_device')
 
   def policy_backward_norm(self, n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale,
                            d_table, obs_clip=10.0, d_cadv=None, d_cret=None, clip=0.2, vf_coef=0.5, cvf_coef=0.5, ent_coef=0.0,
-                           adv_affine=(1.0, 0.0), cadv_affine=(0.0, 0.0), activation=POLICY_RELU, flags=0, max_blocks=0, obs_pitch=None):
+                           adv_affine=(1.0, 0.0), cadv_affine=(0.0, 0.0), activation=POLICY_RELU, flags=0, max_blocks=0, obs_pitch=None,
+                           rows=None):
     """sag_policy_backward_norm_device: policy_backward over observations normalised under d_table and clamped to
-    +-obs_clip where they are staged, as policy_forward_norm does."""
+    +-obs_clip where they are staged, as policy_forward_norm does.  rows=(d_rows, n_index): sag_policy_backward_rows_device
+    with the table."""
     ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
     d = PolicyGradDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(hidden),
                        int(activation), int(flags), int(max_blocks), float(clip), float(vf_coef), float(cvf_coef), float(ent_coef),
                        float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
                        *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
+    if rows is not None:
+      self._check(self.lib.sag_policy_backward_rows_device(self.h, C.byref(d), ptr(rows[0]), int(rows[1]), ptr(d_table), float(obs_clip)),
+                  'sag_policy_backward_rows_device')
+      return
     self._check(self.lib.sag_policy_backward_norm_device(self.h, C.byref(d), ptr(d_table), float(obs_clip)), 'sag_policy_backward_norm_device')
+
+  def permutation(self, n, draw, d_index):
+    """sag_permutation_device: d_index[0 ... n) (device int32) = a keyed pseudo-random permutation of 0 ... n - 1 under the
+    context key and `draw` (the header defines it bit for bit); enqueued on the context stream - no wait, no host copy."""
+    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
+    self._check(self.lib.sag_permutation_device(self.h, int(n), int(draw) & 0xffffffff, ptr(d_index)), 'sag_permutation_device')
 
   def obs_stats(self, d_state, d_table, d_obs=None, n_rows=0, n_planes=0, pitch=0, obs_pitch=None, eps=1e-8, max_blocks=0, table_only=False):
     """sag_obs_stats_device: the per-column moments of n_planes x n_rows observation rows (planes `pitch` rows, rows obs_pitch

@@ -28,6 +28,7 @@
 #include "sag_policy_grad.hpp"
 #include "sag_learner.hpp"
 #include "sag_obs_norm.hpp"
+#include "sag_shuffle.hpp"
 
 #ifndef SAG_SPLIT_MIN_ENVS
 #define SAG_EARLY_FORK_MIN_ENVS 2097152  // tools/ab.sh run sweep: crossover between 1.5 M and 2 M envs
@@ -1297,7 +1298,9 @@ int sag_policy_forward_norm_device(sag_ctx* c, const sag_policy_desc* d, const f
 // ---- the update (sag_policy_grad.hpp) ----
 namespace {
 
-int policy_backward(sag_ctx* c, const char* who, const sag_policy_grad_desc* d, const float* d_table, float obs_clip) {
+// d_rows == nullptr: the contiguous entry points; otherwise the batch is the n_index entries of the list
+int policy_backward(sag_ctx* c, const char* who, const sag_policy_grad_desc* d, const float* d_table, float obs_clip,
+                    const int32_t* d_rows = nullptr, int32_t n_index = 0) {
   if (!d) return fail(c, SAG_ERR_ARG, "%s: desc is NULL", who);
   if (!d->d_params || !d->d_obs || !d->d_actions || !d->d_logp_old || !d->d_adv || !d->d_ret || !d->d_grad)
     return fail(c, SAG_ERR_ARG, "%s: d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret and d_grad must be given", who);
@@ -1322,8 +1325,10 @@ int policy_backward(sag_ctx* c, const char* who, const sag_policy_grad_desc* d, 
     return fail(c, SAG_ERR_UNSUPPORTED, "%s: hidden = %d: the backward pass is built for hidden <= %d", who, d->hidden, 32 * PGRAD_MAX_TILES);
   HIPCHK(c, hipSetDevice(c->cfg.device));
   const int od = c->rb.obs_dim, nu = c->rb.nu, H = d->hidden, NO = nu + 2;
-  PolicyGradNormArgs a;
-  a.total = (int64_t)d->n_planes * d->n_rows;
+  PolicyGradRowsArgs a;
+  a.limit = (int64_t)d->n_planes * d->n_rows;
+  a.total = d_rows ? (int64_t)n_index : a.limit;
+  a.rows = d_rows;
   a.n_rows = d->n_rows; a.pitch = d->pitch; a.obs_dim = od; a.nu = nu; a.activation = d->activation; a.obs_pitch = d->obs_pitch;
   a.n_params = od * H + H + H * H + H + H * NO + NO + nu;
   a.clip = d->clip; a.vf = d->vf_coef; a.cvf = d->cvf_coef; a.ent = d->ent_coef;
@@ -1341,9 +1346,27 @@ int policy_backward(sag_ctx* c, const char* who, const sag_policy_grad_desc* d, 
   }
   a.part = c->d_pgrad;
   const PolicyGradArgs& plain = a;
+  const PolicyGradNormArgs& norm = a;
   const size_t lds = pgrad_lds_floats(od, H) * sizeof(float);
   const dim3 g((unsigned)grid), block(PGRAD_THREADS);
-  if (!d_table) {
+  if (d_rows) {
+    const size_t ldr = lds + PGRAD_ROWS_LDS_FLOATS * sizeof(float);
+    if (!d_table) {
+      switch (H / 32) {
+        case 1: hipLaunchKernelGGL((k_policy_backward<1, false, true>), g, block, ldr, c->stream, a); break;
+        case 2: hipLaunchKernelGGL((k_policy_backward<2, false, true>), g, block, ldr, c->stream, a); break;
+        case 3: hipLaunchKernelGGL((k_policy_backward<3, false, true>), g, block, ldr, c->stream, a); break;
+        default: hipLaunchKernelGGL((k_policy_backward<4, false, true>), g, block, ldr, c->stream, a); break;
+      }
+    } else {
+      switch (H / 32) {
+        case 1: hipLaunchKernelGGL((k_policy_backward<1, true, true>), g, block, ldr, c->stream, a); break;
+        case 2: hipLaunchKernelGGL((k_policy_backward<2, true, true>), g, block, ldr, c->stream, a); break;
+        case 3: hipLaunchKernelGGL((k_policy_backward<3, true, true>), g, block, ldr, c->stream, a); break;
+        default: hipLaunchKernelGGL((k_policy_backward<4, true, true>), g, block, ldr, c->stream, a); break;
+      }
+    }
+  } else if (!d_table) {
     switch (H / 32) {
       case 1: hipLaunchKernelGGL((k_policy_backward<1>), g, block, lds, c->stream, plain); break;
       case 2: hipLaunchKernelGGL((k_policy_backward<2>), g, block, lds, c->stream, plain); break;
@@ -1352,10 +1375,10 @@ int policy_backward(sag_ctx* c, const char* who, const sag_policy_grad_desc* d, 
     }
   } else {
     switch (H / 32) {
-      case 1: hipLaunchKernelGGL((k_policy_backward<1, true>), g, block, lds, c->stream, a); break;
-      case 2: hipLaunchKernelGGL((k_policy_backward<2, true>), g, block, lds, c->stream, a); break;
-      case 3: hipLaunchKernelGGL((k_policy_backward<3, true>), g, block, lds, c->stream, a); break;
-      default: hipLaunchKernelGGL((k_policy_backward<4, true>), g, block, lds, c->stream, a); break;
+      case 1: hipLaunchKernelGGL((k_policy_backward<1, true>), g, block, lds, c->stream, norm); break;
+      case 2: hipLaunchKernelGGL((k_policy_backward<2, true>), g, block, lds, c->stream, norm); break;
+      case 3: hipLaunchKernelGGL((k_policy_backward<3, true>), g, block, lds, c->stream, norm); break;
+      default: hipLaunchKernelGGL((k_policy_backward<4, true>), g, block, lds, c->stream, norm); break;
     }
   }
   HIPCHK(c, hipGetLastError());
@@ -1377,6 +1400,31 @@ int sag_policy_backward_norm_device(sag_ctx* c, const sag_policy_grad_desc* d, c
   const char* who = "sag_policy_backward_norm_device";
   if (int rc = norm_args_ok(c, who, d_table, clip)) return rc;
   return policy_backward(c, who, d, d_table, clip);
+}
+
+int sag_policy_backward_rows_device(sag_ctx* c, const sag_policy_grad_desc* d, const int32_t* d_rows, int32_t n_index, const float* d_table,
+                                    float obs_clip) {
+  if (!c) return SAG_ERR_ARG;
+  const char* who = "sag_policy_backward_rows_device";
+  if (!d_rows || misaligned(d_rows, 4)) return fail(c, SAG_ERR_ARG, "%s: d_rows is NULL or not 4-byte aligned", who);
+  if (n_index < 1) return fail(c, SAG_ERR_ARG, "%s: n_index = %d", who, n_index);
+  if (d_table) {
+    if (int rc = norm_args_ok(c, who, d_table, obs_clip)) return rc;
+    if (!std::isfinite(obs_clip)) return fail(c, SAG_ERR_ARG, "%s: obs_clip = %g is not finite", who, (double)obs_clip);
+  }
+  return policy_backward(c, who, d, d_table, d_table ? obs_clip : 0.0f, d_rows, n_index);
+}
+
+// ---- the row list of a shuffled epoch (sag_shuffle.hpp) ----
+int sag_permutation_device(sag_ctx* c, int32_t n, uint32_t draw, int32_t* d_index) {
+  if (!c) return SAG_ERR_ARG;
+  if (!d_index || misaligned(d_index, 4)) return fail(c, SAG_ERR_ARG, "sag_permutation_device: d_index is NULL or not 4-byte aligned");
+  if (n < 1) return fail(c, SAG_ERR_ARG, "sag_permutation_device: n = %d", n);
+  HIPCHK(c, hipSetDevice(c->cfg.device));
+  hipLaunchKernelGGL(k_permutation, dim3((unsigned)(((uint32_t)n + SHUFFLE_THREADS - 1) / SHUFFLE_THREADS)), dim3(SHUFFLE_THREADS), 0, c->stream,
+                     (uint32_t)n, shuffle_bits(n), draw, (uint32_t)(c->cfg.seed & 0xffffffffu), (uint32_t)(c->cfg.seed >> 32), d_index);
+  HIPCHK(c, hipGetLastError());
+  return SAG_OK;
 }
 
 int sag_adam_device(sag_ctx* c, const sag_adam_desc* d) {

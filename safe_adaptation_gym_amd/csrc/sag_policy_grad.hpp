@@ -2,7 +2,8 @@
 //   k_policy_backward<NT>   the gradient of the PPO-Lagrangian loss through the MLP of sag_policy.hpp, hidden = 32 * NT <= 128:
 //                           persistent blocks of four wavefronts, one partial [n_params + 8] per block, no atomics
 //                           (k_policy_backward<NT, true>: over observations normalised where they are staged,
-//                           sag_policy_backward_norm_device)
+//                           sag_policy_backward_norm_device; k_policy_backward<NT, NORM, true>: over a list of rows gathered
+//                           where they are staged, sag_policy_backward_rows_device)
 //   k_policy_grad_reduce    the partials summed in ascending block order into d_grad
 //   k_adam                  the elementwise optimiser step
 // Per tile of 32 rows a block keeps four images in LDS, all [row][unit] at a pitch of 4 (mod 32) floats: X (the staged
@@ -55,6 +56,12 @@ struct PolicyGradNormArgs : PolicyGradArgs {
   const float* table;   // mean [obs_dim], rstd [obs_dim]
   float obs_clip;
 };
+// sag_policy_backward_rows_device: `total` is the length of the row list, `limit` = n_planes * n_rows what an entry must be below
+struct PolicyGradRowsArgs : PolicyGradNormArgs {
+  const int32_t* rows;
+  int64_t limit;
+};
+constexpr int PGRAD_ROWS_LDS_FLOATS = 2 * POLICY_ROWS;   // the ROWS instances' 32 source rows, int64, behind the four images
 
 // Between two output tiles the compiler must not hoist the next tile's 32 LDS reads above this tile's MFMAs: with nine tiles
 // unrolled it otherwise keeps hundreds of loaded operands live and spills the accumulators.
@@ -134,12 +141,17 @@ __device__ inline void pgrad_put_tile(float* out, int ld, int K, int J, int ki, 
   }
 }
 
-template <bool NORM> struct PolicyGradArgsOf { typedef PolicyGradArgs type; };
-template <> struct PolicyGradArgsOf<true> { typedef PolicyGradNormArgs type; };
+template <bool NORM, bool ROWS = false> struct PolicyGradArgsOf { typedef PolicyGradArgs type; };
+template <> struct PolicyGradArgsOf<true, false> { typedef PolicyGradNormArgs type; };
+template <bool NORM> struct PolicyGradArgsOf<NORM, true> { typedef PolicyGradRowsArgs type; };
 
 // NORM: sag_policy_backward_norm_device; the plain instances are what they were before the switch existed
-template <int NT, bool NORM = false>
-__global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(typename PolicyGradArgsOf<NORM>::type p) {
+// ROWS: sag_policy_backward_rows_device - batch row j is logical element rows[j] of the planes.  A tile's 32 entries are turned
+//       into source rows once, into 32 words of LDS behind the images (-1: absent - at or beyond the list's end, or an entry
+//       outside the planes), and the staging loop and the head lane both take `src` from there.  Everything else is the code of
+//       the contiguous instances, which the switch leaves what they were.
+template <int NT, bool NORM = false, bool ROWS = false>
+__global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(typename PolicyGradArgsOf<NORM, ROWS>::type p) {
 #pragma clang fp contract(off)
   constexpr int H = 32 * NT, PH = H + 4, PD = PGRAD_DO_PITCH;
   constexpr int T3 = (NT + PGRAD_WAVES - 1) / PGRAD_WAVES, T2 = (NT * NT + PGRAD_WAVES - 1) / PGRAD_WAVES, T1 = NT;   // tiles per wavefront
@@ -154,6 +166,8 @@ __global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(typename Poli
   float* DO = I2 + POLICY_ROWS * PH;
   const int lds_floats = POLICY_ROWS * (PX + 2 * PH + PD);
   for (int k = tid; k < lds_floats; k += PGRAD_THREADS) lds[k] = 0.0f;   // the pad columns of X stay zero
+  int64_t* SRC = reinterpret_cast<int64_t*>(lds + lds_floats);   // ROWS only (lds_floats is a multiple of 32: aligned)
+  (void)SRC;
 
   const float* W1 = p.params;
   const float* b1 = W1 + (size_t)od * H;
@@ -198,11 +212,31 @@ __global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(typename Poli
   const int64_t n_tiles = (p.total + POLICY_ROWS - 1) / POLICY_ROWS;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t g0 = tile * POLICY_ROWS;
+    if constexpr (ROWS) {   // (the barrier at the end of the tile before has every reader of SRC behind it)
+      if (tid < POLICY_ROWS) {
+        int64_t s = -1;
+        if (g0 + tid < p.total) {
+          const int64_t e = p.rows[g0 + tid];
+          if (e >= 0 && e < p.limit) {
+            const int64_t plane = e / p.n_rows;
+            s = plane * p.pitch + (e - plane * p.n_rows);
+          }
+        }
+        SRC[tid] = s;
+      }
+      __syncthreads();
+    }
     for (int piece = tid; piece < POLICY_ROWS * Q; piece += PGRAD_THREADS) {
       const int r = piece / Q, q = piece - r * Q;
       const int64_t g = g0 + r;
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);   // rows at or beyond the last are not read
-      if (g < p.total) {
+      if constexpr (ROWS) {
+        const int64_t src = SRC[r];
+        if (src >= 0) {
+          v = *reinterpret_cast<const float4*>(p.obs + (size_t)src * (size_t)p.obs_pitch + 4 * q);
+          if constexpr (NORM) v = obs_norm_piece(v, p.table, od, q, p.obs_clip);
+        }
+      } else if (g < p.total) {
         const int64_t plane = g / p.n_rows;
         const int64_t src = plane * p.pitch + (g - plane * p.n_rows);
         v = *reinterpret_cast<const float4*>(p.obs + (size_t)src * (size_t)p.obs_pitch + 4 * q);
@@ -243,9 +277,20 @@ __global__ __launch_bounds__(PGRAD_THREADS) void k_policy_backward(typename Poli
       for (int u = 0; u < 12; u++) mean[u] = u < nu ? d[u] : 0.0f;
 #pragma unroll
       for (int k = 0; k < PD; k += 4) *reinterpret_cast<float4*>(d + k) = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (g < p.total) {
-        const int64_t plane = g / p.n_rows;
-        const size_t src = (size_t)(plane * p.pitch + (g - plane * p.n_rows));
+      bool present;
+      size_t src = 0;
+      if constexpr (ROWS) {
+        const int64_t s = SRC[tid];
+        present = s >= 0;
+        src = (size_t)s;
+      } else {
+        present = g < p.total;
+        if (present) {
+          const int64_t plane = g / p.n_rows;
+          src = (size_t)(plane * p.pitch + (g - plane * p.n_rows));
+        }
+      }
+      if (present) {
         float ss = 0.0f, slog = 0.0f;
         float zeta[12], istd[12];
 #pragma unroll

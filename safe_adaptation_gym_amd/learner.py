@@ -8,7 +8,9 @@ Every round is two enqueued calls - the gradient of one minibatch read in place 
 (sag_policy_backward_device) and one Adam step on the policy's parameters (sag_adam_device), with the global-norm clip
 (sag_grad_clip_device) between them where asked for; the advantage's moments, the Lagrange multiplier's step and the mixed
 advantage (sag_moments_device, sag_lagrange_device, sag_advantage_mix_device) are enqueued once ahead of the rounds and stay on
-the device.  The update joins the stream once, at its end.  NumPy only; no torch."""
+the device.  With shuffle=True every epoch starts with one more enqueued call, the permutation of all T x N rows
+(sag_permutation_device), and a round's minibatch is a slice of it (sag_policy_backward_rows_device).  The update joins the
+stream once, at its end.  NumPy only; no torch."""
 import numpy as np
 
 from safe_adaptation_gym_amd import _native as nat
@@ -25,7 +27,7 @@ class PPOLearner:
   """learner = PPOLearner(pi, buf, lr=3e-4, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5, cost_vf_coef=0.5, ent_coef=0.0,
                           cost_weight=0.0, betas=(0.9, 0.999), eps=1e-8, std_min=1e-3, normalize_advantage=False,
                           cost_advantage='center', max_grad_norm=None, cost_budget=None, lagrange_lr=0.05, lagrange_max=inf,
-                          update_obs_stats=True)
+                          update_obs_stats=True, shuffle=False, shuffle_draw=0)
 
   pi: an MLPPolicy (hidden <= 128), buf: a RolloutBuffer of the same env.  The learner owns the Adam moments and the step count.
 
@@ -55,12 +57,23 @@ class PPOLearner:
   epoch of one update see one table - so buf.logp and the first epoch's ratio agree - and the next collect sees statistics
   that include this batch.  Still one host join per update.  The very first collect runs under the identity table unless
   pi.update_obs_stats() was called on a warm-up rollout.  update_obs_stats=False turns the hook off; so does
-  pi.obs_norm_frozen.  With a policy that does not normalise, update() enqueues what it did before."""
+  pi.obs_norm_frozen.  With a policy that does not normalise, update() enqueues what it did before.
+
+  shuffle=True draws every epoch's minibatches from a fresh random permutation of all n = T x N stored rows, as a textbook
+  PPO does, instead of cutting the buffer into ranges of planes: the learner owns an int32 device array of n entries, every
+  epoch enqueues one sag_permutation_device(n, shuffle_draw) into it and advances shuffle_draw by one, and minibatch m is the
+  list slice [n m // M, n (m + 1) // M), read in place through sag_policy_backward_rows_device with scale = 1 / its length -
+  no upload, no gathered copy (ValueError if minibatches > T x N).  learner.shuffle_draw is the next epoch's draw: save it
+  with a checkpoint and pass it back as shuffle_draw= (or assign it) to continue the same sequence of permutations.  The
+  permutation is a keyed pseudo-random one under the env's seed (include/sag.h).  Everything else - the mixed advantage, the
+  clip, Adam, the observation statistics, the single host join - is as without it; ranges() describes shuffle=False only."""
 
   def __init__(self, pi, buf, lr=3e-4, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5, cost_vf_coef=0.5, ent_coef=0.0,
                cost_weight=0.0, betas=(0.9, 0.999), eps=1e-8, std_min=1e-3, normalize_advantage=False, cost_advantage='center',
-               max_grad_norm=None, cost_budget=None, lagrange_lr=0.05, lagrange_max=float('inf'), update_obs_stats=True):
+               max_grad_norm=None, cost_budget=None, lagrange_lr=0.05, lagrange_max=float('inf'), update_obs_stats=True,
+               shuffle=False, shuffle_draw=0):
     self.update_obs_stats = bool(update_obs_stats)
+    self.shuffle, self.shuffle_draw = bool(shuffle), int(shuffle_draw) & 0xffffffff
     if buf.env is not pi.env:
       raise ValueError('PPOLearner: the policy and the buffer belong to different envs')
     if pi.hidden > 128:
@@ -68,8 +81,13 @@ class PPOLearner:
     epochs, minibatches = int(epochs), int(minibatches)
     if epochs < 1 or minibatches < 1:
       raise ValueError(f'PPOLearner: epochs={epochs}, minibatches={minibatches}')
-    if minibatches > buf.T:
-      raise ValueError(f'PPOLearner: minibatches={minibatches} of a buffer of T={buf.T} planes')
+    if self.shuffle and buf.T * buf.N >= 2**31:
+      raise ValueError(f'PPOLearner: shuffle=True over {buf.T} x {buf.N} rows: the row list is int32')
+    if self.shuffle and pi.normalize_observations and not np.isfinite(pi.obs_clip):
+      raise ValueError('PPOLearner: shuffle=True with a normalising policy needs a finite obs_clip (sag_policy_backward_rows_device)')
+    if minibatches > (buf.T * buf.N if self.shuffle else buf.T):
+      raise ValueError(f'PPOLearner: minibatches={minibatches} of a buffer of T={buf.T} planes' +
+                       (f' x N={buf.N} rows' if self.shuffle else ''))
     if not (0 < clip < 1) or not lr > 0 or not eps > 0 or not std_min > 0 or not all(0 <= b < 1 for b in betas):
       raise ValueError(f'PPOLearner: lr={lr}, clip={clip}, betas={betas}, eps={eps}, std_min={std_min}')
     if cost_advantage not in COST_ADVANTAGE:
@@ -92,7 +110,9 @@ class PPOLearner:
     self._m, self._v = c.dev_alloc(n * 4), c.dev_alloc(n * 4)
     c.dev_upload(self._m, np.zeros(n, np.float32))
     c.dev_upload(self._v, np.zeros(n, np.float32))
-    self._words = self._mixed = None
+    self._words = self._mixed = self._index = None
+    if self.shuffle:
+      self._index = c.dev_alloc(buf.T * buf.N * 4)   # [T x N] int32: the epoch's permutation
     if self.normalize_advantage or self.max_grad_norm is not None or self.cost_budget is not None:
       self._words = c.dev_alloc(_WORDS * 4)
       c.dev_upload(self._words, np.zeros(_WORDS, np.float32))
@@ -159,18 +179,26 @@ class PPOLearner:
     cost = 'cadv' in out and 'cret' in out
     b1, b2 = self.betas
     mixed = self._prepare(out, cost) if self._mixes() else None
+    n, M = buf.T * buf.N, self.minibatches
     for _ in range(self.epochs):
-      for t0, t1 in self.ranges():
+      if self.shuffle:   # minibatch m: entries n m // M ... n (m + 1) // M - 1 of this epoch's permutation, over all T planes
+        c.permutation(n, self.shuffle_draw, self._index)
+        self.shuffle_draw = (self.shuffle_draw + 1) & 0xffffffff
+        rounds = [(0, buf.T, (self._index.value + 4 * (n * m // M), n * (m + 1) // M - n * m // M)) for m in range(M)]
+      else:
+        rounds = [(t0, t1, None) for t0, t1 in self.ranges()]
+      for t0, t1, rows in rounds:
         cut = lambda v: plane_range(v, t0, t1)   # noqa: E731
+        kw = dict(scale=1.0 / ((t1 - t0) * buf.N)) if rows is None else dict(scale=1.0 / rows[1], rows=rows)
         if mixed is None:
           pi.backward(cut(buf.obs), cut(buf.actions), cut(buf.logp), cut(out['adv']), cut(out['ret']),
                       cut(out['cadv']) if cost else None, cut(out['cret']) if cost else None, clip=self.clip, vf_coef=self.vf_coef,
                       cost_vf_coef=self.cost_vf_coef, ent_coef=self.ent_coef, adv_affine=(1.0, 0.0), cadv_affine=(self.cost_weight, 0.0),
-                      scale=1.0 / ((t1 - t0) * buf.N))
+                      **kw)
         else:   # the cost advantage is inside `mixed`; the cost critic still learns from cret
           pi.backward(cut(buf.obs), cut(buf.actions), cut(buf.logp), cut(mixed), cut(out['ret']), None, cut(out['cret']) if cost else None,
                       clip=self.clip, vf_coef=self.vf_coef, cost_vf_coef=self.cost_vf_coef, ent_coef=self.ent_coef, adv_affine=(1.0, 0.0),
-                      cadv_affine=(0.0, 0.0), scale=1.0 / ((t1 - t0) * buf.N))
+                      cadv_affine=(0.0, 0.0), **kw)
         if self.max_grad_norm is not None:
           c.grad_clip(pi.n_params, pi._gbuf, self._word(_CLIP), self.max_grad_norm)
         self.t += 1
@@ -196,10 +224,11 @@ class PPOLearner:
   def close(self):
     c = getattr(self, '_ctx', None)
     if c is not None and c.h:
-      for p in (getattr(self, '_m', None), getattr(self, '_v', None), getattr(self, '_words', None), getattr(self, '_mixed', None)):
+      for p in (getattr(self, '_m', None), getattr(self, '_v', None), getattr(self, '_words', None), getattr(self, '_mixed', None),
+                getattr(self, '_index', None)):
         if p is not None:
           c.dev_free(p)
-    self._m = self._v = self._words = self._mixed = self._ctx = None
+    self._m = self._v = self._words = self._mixed = self._index = self._ctx = None
 
   def __del__(self):
     try:

@@ -231,14 +231,36 @@ class MLPPolicy:
       raise ValueError(f'MLPPolicy.backward: {what}: rows must be contiguous and planes a whole number of rows apart')
     return ptr, int(shape[0]), int(shape[1]), strides[0] // dense[0]
 
+  def _row_list(self, rows):
+    """(pointer, count) of a row list: a contiguous device int32 view [count], or such a pair itself."""
+    if isinstance(rows, tuple) and len(rows) == 2:
+      p, count = rows
+      p, count = int(p.value if hasattr(p, 'value') else p), int(count)
+    else:
+      try:
+        p = nat.device_pointer(rows)
+      except ValueError as e:
+        raise ValueError(f'MLPPolicy.backward: rows: {e}') from None
+      cai = rows.__cuda_array_interface__
+      if np.dtype(cai['typestr']) != np.dtype('<i4') or len(cai['shape']) != 1:
+        raise ValueError(f"MLPPolicy.backward: rows must be int32 of shape (count,), not {cai['typestr']} {tuple(cai['shape'])}")
+      count = int(cai['shape'][0])
+    if count < 1 or p % 4:
+      raise ValueError(f'MLPPolicy.backward: rows: {count} entries at a pointer that must be 4-byte aligned')
+    return p, count
+
   def backward(self, obs, actions, logp_old, adv, ret, cadv=None, cret=None, *, clip, vf_coef, cost_vf_coef, ent_coef,
-               adv_affine=(1.0, 0.0), cadv_affine=(0.0, 0.0), scale, accumulate=False):
+               adv_affine=(1.0, 0.0), cadv_affine=(0.0, 0.0), scale, accumulate=False, rows=None):
     """The gradient of the PPO-Lagrangian loss over stored rows into `grad` (sag_policy_backward_device; include/sag.h defines
     the loss), enqueued on the stream.  Every input is a time-major device view [planes, rows, ...] - a RolloutBuffer's obs,
     actions, logp and the views advantages() returns, or a range of their planes (plane_range) - and all must share planes, rows
     and the pitch between planes; ValueError otherwise, or for a hidden size the backward does not support (> 128).  The
     advantage is adv_affine[0] * (adv - adv_affine[1]) - cadv_affine[0] * (cadv - cadv_affine[1]); scale is 1 / (rows of the
-    whole batch); accumulate=True adds to what `grad` holds."""
+    whole batch); accumulate=True adds to what `grad` holds.
+    rows: a contiguous device int32 view [count], or (pointer, count) - the batch is then the `count` rows that the list names,
+    entry e being row e % rows of plane e // rows of the views, gathered in place (sag_policy_backward_rows_device; an entry
+    outside the views is a row that is absent).  A slice of the list sag_permutation_device wrote is a shuffled minibatch."""
+    listed = None if rows is None else self._row_list(rows)
     if self.hidden > 128:
       raise ValueError(f'MLPPolicy.backward: hidden={self.hidden}: the backward pass supports hidden <= 128')
     given = [('obs', obs, (self.obs_dim,)), ('actions', actions, (self.nu,)), ('logp_old', logp_old, ()), ('adv', adv, ()),
@@ -262,6 +284,8 @@ class MLPPolicy:
     kw = dict(d_cadv=ptr['cadv'], d_cret=ptr['cret'], clip=clip, vf_coef=vf_coef, cvf_coef=cost_vf_coef, ent_coef=ent_coef,
               adv_affine=adv_affine, cadv_affine=cadv_affine, activation=ACTIVATIONS[self.activation],
               flags=nat.POLICY_GRAD_ACCUMULATE if accumulate else 0)
+    if listed is not None:
+      kw['rows'] = listed
     if self.normalize_observations:
       self._ctx.policy_backward_norm(*args, self._obs_table, self.obs_clip, **kw)
     else:

@@ -16,7 +16,19 @@ back to back and one sag_wait, wall time per call, the median (min ... max) over
   update     sag.PPOLearner(hidden 64, epochs 1, minibatches 8: eight rounds of one plane each) with normalize_advantage,
              max_grad_norm and cost_budget on, and with all off (the calls of the commit before: tools/ppo_time.py's backward +
              Adam on the same rows is what one of its rounds is compared with)
-profiles/learner_options_time.txt is such a table."""
+profiles/learner_options_time.txt is such a table.
+
+  python tools/learner_time.py [out.txt] --shuffle [--robot point|doggo] [--envs 4096] [--steps 64] [--rounds 9] [--calls 20]
+
+What shuffled-row minibatches cost (csrc/sag_shuffle.hpp, the ROWS instances of csrc/sag_policy_grad.hpp): one process, a
+collected rollout of --steps planes of --envs rows, hidden 64, 8 minibatches.
+  backward   one minibatch of steps / 8 contiguous planes: sag_policy_backward_device (the round of shuffle=False)
+  sorted     the same rows through sag_policy_backward_rows_device under the list 0, 1, 2, ...: the list's own cost, no gather
+  gathered   as many rows through a slice of a permutation: every row a read of 240 to 416 B at a random address
+  permute    one sag_permutation_device over all steps x envs entries
+  update     PPOLearner.update(), 1 epoch x 8 minibatches, shuffle=False and shuffle=True
+Under SAG_LIB=<a library of the commit before> the two entry points are missing and only `backward` and the update with
+shuffle=False are measured: the contiguous path of that commit.  profiles/shuffle_time.txt holds such tables."""
 import json
 import os
 import subprocess
@@ -93,9 +105,87 @@ def child(n, rounds, calls):
   pi.close(); buf.close()
 
 
+def shuffle_child(robot, n, steps, rounds, calls):
+  import numpy as np
+  import safe_adaptation_gym_amd as sag
+  from safe_adaptation_gym_amd import _native as nat
+  from safe_adaptation_gym_amd.policy import plane_range
+  env = sag.make(robot, 'go_to_goal', seed=12345, n_envs=n, device_buffers=True, device_reset=True, time_limit=LIMIT, auto_reset=True,
+                 final_observation=True)
+  env.reset()
+  c = env._ctx[0]
+  pi = sag.MLPPolicy(env, hidden=HIDDEN, activation='tanh', seed=1)
+  buf = sag.RolloutBuffer(env, steps=steps)
+  buf.collect(pi)
+  pi.evaluate(buf)
+  adv = buf.advantages(buf.value, buf.cost_value, buf.final_value, buf.final_cost_value)
+  buf.wait()
+  N, P, M = buf.N, buf.P, 8
+  total, per = steps * N, steps // M
+  have = hasattr(c.lib, 'sag_permutation_device')
+  out = {'P': P, 'params': pi.n_params, 'have': have}
+  kw = dict(clip=0.2, vf_coef=0.5, cost_vf_coef=0.5, ent_coef=0.0, cadv_affine=(0.1, 0.0))
+  cut = lambda v, t0, t1: plane_range(v, t0, t1)   # noqa: E731
+  views = lambda t0, t1: [cut(v, t0, t1) for v in (buf.obs, buf.actions, buf.logp, adv['adv'], adv['ret'], adv['cadv'], adv['cret'])]   # noqa: E731
+  part, whole = views(per, 2 * per), views(0, steps)
+  out['backward'] = _timed(c, calls, rounds, lambda: pi.backward(*part, scale=1.0 / (per * N), **kw))
+  if have:
+    index = c.dev_alloc(total * 4)
+    c.dev_upload(index, np.arange(total, dtype=np.int32))
+    rows = (index.value + 4 * per * N, per * N)   # the same rows as `backward`
+    out['sorted'] = _timed(c, calls, rounds, lambda: pi.backward(*whole, scale=1.0 / (per * N), rows=rows, **kw))
+    out['permute'] = _timed(c, calls, rounds, lambda: c.permutation(total, 7, index))
+    perm = c.dev_download(index, (total,), np.int32)
+    assert np.array_equal(np.sort(perm), np.arange(total))   # (the tests compare values: here only that the timed call was the kernel)
+    out['gathered'] = _timed(c, calls, rounds, lambda: pi.backward(*whole, scale=1.0 / (per * N), rows=rows, **kw))
+    c.dev_free(index)
+  few = calls if total <= 65536 else max(4, calls // 8)
+  before = pi.get_params()
+  for name, opt in (('update_off', {}), ('update_shuffle', dict(shuffle=True))):
+    if opt and not have:
+      continue
+    pi.set_params(before)
+    learner = sag.PPOLearner(pi, buf, epochs=1, minibatches=M, lr=1e-5, cost_weight=0.1, **opt)
+    out[name] = _timed(c, few, rounds, lambda: learner.update(adv))
+    learner.close()
+  print(json.dumps(out), flush=True)
+  pi.close(); buf.close()
+
+
+def shuffle_main(a, path):
+  opt = lambda k, d: a[a.index(k) + 1] if k in a else d   # noqa: E731
+  robot, n, steps = opt('--robot', 'point'), int(opt('--envs', 4096)), int(opt('--steps', 64))
+  rounds, calls = int(opt('--rounds', 9)), int(opt('--calls', 20))
+  r = subprocess.run([sys.executable, os.path.abspath(__file__), '--shuffle-child', robot, str(n), str(steps), str(rounds), str(calls)],
+                     capture_output=True, text=True, timeout=1100)
+  if r.returncode != 0:
+    sys.exit(f'{robot} ended with {r.returncode}:\n{r.stdout[-1000:]}{r.stderr[-3000:]}')
+  m = json.loads(r.stdout.strip().splitlines()[-1])
+  fmt = lambda k: f'{m[k][0]:9.4f} ms ({m[k][1]:.4f} ... {m[k][2]:.4f})'   # noqa: E731
+  rows = steps // 8 * n
+  lines = [f'{robot}, {steps} planes of {n} rows (pitch {m["P"]}) from a collected rollout, hidden {HIDDEN} ({m["params"]} parameters), library '
+           f'{os.path.basename(os.environ.get("SAG_LIB") or "libsag.so")}.  Wall ms per call, {calls} calls back to back and one sag_wait, median (min ... max) of '
+           f'{rounds} rounds after 2',
+           f'  backward, {steps // 8} contiguous planes = {rows} rows    {fmt("backward")}']
+  if m['have']:
+    lines += [f'  sorted list of the same {rows} rows          {fmt("sorted")} = {m["sorted"][0] / m["backward"][0]:.3f} x',
+              f'  gathered, {rows} entries of a permutation   {fmt("gathered")} = {m["gathered"][0] / m["backward"][0]:.3f} x',
+              f'  permutation of {steps * n} entries            {fmt("permute")}']
+  lines += [f'  update(), shuffle=False, 8 rounds           {fmt("update_off")} = {m["update_off"][0] / 8:.4f} ms per round']
+  if m['have']:
+    lines += [f'  update(), shuffle=True,  8 rounds           {fmt("update_shuffle")} = {m["update_shuffle"][0] / 8:.4f} ms per round']
+  print('\n'.join(lines), flush=True)
+  if path:
+    os.makedirs(os.path.dirname(path) or '.', exist_ok=True)
+    with open(path, 'a') as fh:
+      fh.write('\n'.join(lines) + '\n')
+
+
 def main():
   a = sys.argv[1:]
   opt = lambda k, d: a[a.index(k) + 1] if k in a else d   # noqa: E731
+  if '--shuffle' in a:
+    return shuffle_main(a, a[0] if a and not a[0].startswith('--') else None)
   rounds, calls, rows = int(opt('--rounds', 9)), int(opt('--calls', 20)), opt('--rows', None)
   path = a[0] if a and not a[0].startswith('--') else None
   lines = [f'Point (obs_dim 60), {T} planes of N rows from a collected rollout (time limit {LIMIT}), hidden {HIDDEN}; one process per size.  Wall ms per '
@@ -133,5 +223,8 @@ if __name__ == '__main__':
   if len(sys.argv) > 1 and sys.argv[1] == '--child':
     sys.path.insert(0, ROOT)
     child(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]))
+  elif len(sys.argv) > 1 and sys.argv[1] == '--shuffle-child':
+    sys.path.insert(0, ROOT)
+    shuffle_child(sys.argv[2], *[int(x) for x in sys.argv[3:7]])
   else:
     main()
