@@ -2,7 +2,9 @@
 
 There is no CPU fallback: if the HIP library is missing or no MI355X is visible,
 every entry point raises."""
+import collections
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -27,22 +29,6 @@ F_BOUND = 141
 
 ROBOT_IDS = {'point': 0, 'car': 1, 'doggo': 2}
 FORK_SAME_STREAM = 1   # enum sag_fork_flags
-
-EXPORTS = [
-    'sag_robot_info', 'sag_create', 'sag_destroy', 'sag_last_error', 'sag_set_layout',
-    'sag_reset', 'sag_get_state', 'sag_set_state', 'sag_step', 'sag_step_device', 'sag_wait',
-    'sag_observe', 'sag_set_ext_contacts', 'sag_lidar_cost', 'sag_lidar_cost_device', 'sag_set_seed', 'sag_dev_alloc', 'sag_dev_free', 'sag_dev_upload',
-    'sag_dev_download', 'sag_dev_fill_actions', 'sag_kernel_time_ms', 'sag_enable_timing', 'sag_busy_count', 'sag_debug_cycles', 'sag_render_rgb', 'sag_render_rgb_device', 'sag_render', 'sag_render_device', 'sag_render_rows_device', 'sag_render_envs', 'sag_render_aux', 'sag_render_aux_device', 'sag_debug_doggo_coop',
-    'sag_device_count', 'sag_world_config_default', 'sag_sample_layouts', 'sag_sample_layouts_desc', 'sag_task_desc_default', 'sag_task_desc_check',
-    'sag_set_tasks', 'sag_reset_device', 'sag_reset_device_async', 'sag_reset_device_counts', 'sag_episode_track_device',
-    'sag_episode_clear', 'sag_copy_rows_device', 'sag_fork_device', 'sag_fork_counts', 'sag_wait_for', 'sag_plan_sample_device', 'sag_plan_score_device',
-    'sag_plan_refit_device', 'sag_plan_shift_device', 'sag_plan_clear_device', 'sag_append_rows_device', 'sag_gae_device',
-    'sag_policy_forward_device', 'sag_policy_backward_device', 'sag_adam_device',
-    'sag_moments_device', 'sag_advantage_mix_device', 'sag_lagrange_device', 'sag_grad_clip_device',
-    'sag_obs_stats_device', 'sag_policy_forward_norm_device', 'sag_policy_backward_norm_device',
-    'sag_permutation_device', 'sag_policy_backward_rows_device'
-]
-
 
 class SagError(RuntimeError):
   pass
@@ -129,106 +115,6 @@ POLICY_MEAN = 1                   # enum sag_policy_flags
 POLICY_GRAD_ACCUMULATE = 1        # enum sag_policy_grad_flags
 POLICY_GRAD_STATS = 8             # words behind the gradient
 
-_lib = None
-
-
-def load():
-  """Load libsag.so; raises SagError (never falls back) if it is not there."""
-  global _lib
-  if _lib is not None:
-    return _lib
-  if not os.path.exists(LIB_PATH):
-    raise SagError(
-        f'{LIB_PATH} not found: build it with `python -m safe_adaptation_gym_amd.build` '
-        '(hipcc, --offload-arch=gfx950). There is no CPU fallback.')
-  lib = C.CDLL(LIB_PATH)
-  vp, fp, ip = C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)
-  up, bp = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
-  lib.sag_last_error.restype = C.c_char_p
-  lib.sag_last_error.argtypes = [vp]
-  lib.sag_robot_info.argtypes = [C.c_int32, ip, C.POINTER(C.c_double)]
-  lib.sag_create.argtypes = [C.POINTER(_Config), C.POINTER(vp)]
-  lib.sag_destroy.argtypes = [vp]
-  lib.sag_set_layout.argtypes = [vp, ip, C.c_int32, fp, ip]
-  lib.sag_set_state.argtypes = [vp, ip, C.c_int32, fp, ip]
-  lib.sag_get_state.argtypes = [vp, ip, C.c_int32, fp, ip]
-  lib.sag_reset.argtypes = [vp, ip, C.c_int32]
-  lib.sag_step.argtypes = [vp, fp, fp, up, C.c_int32, C.c_int32, fp, fp, bp, bp, bp, ip]
-  lib.sag_step_device.argtypes = [vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp]
-  lib.sag_wait.argtypes = [vp]
-  lib.sag_observe.argtypes = [vp, fp]
-  lib.sag_set_ext_contacts.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
-  lib.sag_lidar_cost.argtypes = [vp, C.c_int32, C.c_int32, fp, fp, bp, C.c_float, fp, ip, bp]
-  lib.sag_lidar_cost_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, vp, vp, vp]
-  lib.sag_set_seed.argtypes = [vp, C.c_uint64]
-  lib.sag_dev_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-  lib.sag_dev_free.argtypes = [vp, vp]
-  lib.sag_dev_upload.argtypes = [vp, vp, vp, C.c_uint64]
-  lib.sag_dev_download.argtypes = [vp, vp, vp, C.c_uint64]
-  lib.sag_dev_fill_actions.argtypes = [vp, vp, C.c_uint32]
-  lib.sag_kernel_time_ms.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-  lib.sag_enable_timing.argtypes = [vp, C.c_int32]
-  lib.sag_busy_count.argtypes = [vp, C.POINTER(C.c_int32)]
-  lib.sag_render_rgb.argtypes = [vp, C.POINTER(C.c_uint8)]
-  lib.sag_render_rgb_device.argtypes = [vp, vp]
-  lib.sag_render.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]
-  lib.sag_render_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp]
-  lib.sag_render_rows_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
-  lib.sag_render_envs.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, C.POINTER(C.c_uint8)]
-  lib.sag_render_aux_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp]
-  lib.sag_render_aux.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, ip, C.c_int32, vp]
-  lib.sag_debug_doggo_coop.argtypes = [vp, C.POINTER(C.c_double)]
-  lib.sag_debug_cycles.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.c_int32]
-  lib.sag_world_config_default.argtypes = [C.POINTER(WorldConfig)]
-  lib.sag_world_config_default.restype = None
-  lib.sag_sample_layouts.argtypes = [C.c_int32, C.c_int32, up, ip, C.POINTER(WorldConfig), C.c_int32,
-                                     C.c_int32, fp, ip, up, ip, ip, C.POINTER(C.c_double), ip, C.c_int32]
-  lib.sag_set_tasks.argtypes = [vp, vp, C.c_int32, ip, C.POINTER(WorldConfig), C.c_int32]
-  lib.sag_reset_device.argtypes = [vp, C.c_int32, C.c_int32, vp, ip, fp]
-  lib.sag_reset_device_async.argtypes = [vp, vp, vp]
-  lib.sag_reset_device_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-  lib.sag_episode_track_device.argtypes = [vp, vp, vp, vp, vp, C.c_int32, vp, vp]
-  lib.sag_episode_clear.argtypes = [vp, vp]
-  lib.sag_copy_rows_device.argtypes = [vp, vp, C.c_int32, vp, vp]
-  lib.sag_fork_device.argtypes = [vp, vp, vp, C.c_int32]
-  lib.sag_fork_counts.argtypes = [vp, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
-  lib.sag_wait_for.argtypes = [vp, vp]
-  lib.sag_plan_sample_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_uint32, vp]
-  lib.sag_plan_score_device.argtypes = [vp, vp, C.c_int32, C.c_float, vp]
-  lib.sag_plan_refit_device.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, C.c_float, vp, vp, vp, vp]
-  lib.sag_plan_shift_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_float]
-  lib.sag_plan_clear_device.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp, C.c_float]
-  lib.sag_append_rows_device.argtypes = [vp, vp, C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp]
-  lib.sag_gae_device.argtypes = [vp, C.POINTER(GaeDesc)]
-  lib.sag_policy_forward_device.argtypes = [vp, C.POINTER(PolicyDesc)]
-  lib.sag_policy_backward_device.argtypes = [vp, C.POINTER(PolicyGradDesc)]
-  lib.sag_adam_device.argtypes = [vp, C.POINTER(AdamDesc)]
-  lib.sag_moments_device.argtypes = [vp, C.POINTER(MomentsDesc)]
-  lib.sag_advantage_mix_device.argtypes = [vp, C.POINTER(AdvantageMixDesc)]
-  lib.sag_lagrange_device.argtypes = [vp, C.POINTER(LagrangeDesc)]
-  lib.sag_grad_clip_device.argtypes = [vp, C.POINTER(GradClipDesc)]
-  # (a SAG_LIB library of an earlier commit lacks some of these: it still loads for an A/B run of the plain paths, and a call
-  # of one of them raises AttributeError)
-  for name, sig in (('sag_obs_stats_device', [vp, C.POINTER(ObsStatsDesc)]),
-                    ('sag_policy_forward_norm_device', [vp, C.POINTER(PolicyDesc), vp, C.c_float]),
-                    ('sag_policy_backward_norm_device', [vp, C.POINTER(PolicyGradDesc), vp, C.c_float]),
-                    ('sag_permutation_device', [vp, C.c_int32, C.c_uint32, vp]),
-                    ('sag_policy_backward_rows_device', [vp, C.POINTER(PolicyGradDesc), vp, C.c_int32, vp, C.c_float])):
-    if hasattr(lib, name):
-      getattr(lib, name).argtypes = sig
-  _lib = lib
-  return lib
-
-
-def robot_info(robot):
-  lib = load()
-  out = (C.c_int32 * 5)()
-  dt = C.c_double()
-  rc = lib.sag_robot_info(ROBOT_IDS[robot] if isinstance(robot, str) else robot, out, C.byref(dt))
-  if rc:
-    raise SagError(f'sag_robot_info failed ({rc})')
-  return dict(nu=out[0], obs_dim=out[1], nstep=out[2], nq=out[3], nv=out[4], dt=dt.value)
-
 
 class TaskDesc(C.Structure):
   """sag_task_desc (include/sag.h)."""
@@ -253,22 +139,132 @@ class TaskDesc(C.Structure):
             for k, _ in self._fields_ if k != 'reserved'}
 
 
+def _signatures():
+  """Every function include/sag.h declares -> (argtypes, restype): the one table load() applies and EXPORTS lists."""
+  i32, u32, u64, f32, vp = C.c_int32, C.c_uint32, C.c_uint64, C.c_float, C.c_void_p
+  fp, ip, up, bp, dp, u64p = (C.POINTER(t) for t in (C.c_float, C.c_int32, C.c_uint32, C.c_uint8, C.c_double, C.c_uint64))
+  cfg, task = C.POINTER(WorldConfig), C.POINTER(TaskDesc)
+  sample_tail = [cfg, i32, i32, fp, ip, up, ip, ip, dp, ip, i32]
+  sigs = {
+      'sag_last_error': ([vp], C.c_char_p),
+      'sag_robot_info': [i32, ip, dp],
+      'sag_create': [C.POINTER(_Config), C.POINTER(vp)],
+      'sag_destroy': [vp],
+      'sag_set_layout': [vp, ip, i32, fp, ip],
+      'sag_set_state': [vp, ip, i32, fp, ip],
+      'sag_get_state': [vp, ip, i32, fp, ip],
+      'sag_reset': [vp, ip, i32],
+      'sag_step': [vp, fp, fp, up, i32, i32, fp, fp, bp, bp, bp, ip],
+      'sag_step_device': [vp, vp, vp, i32, vp, vp, vp, vp, vp],
+      'sag_wait': [vp],
+      'sag_observe': [vp, fp],
+      'sag_set_ext_contacts': [vp, ip, up],
+      'sag_lidar_cost': [vp, i32, i32, fp, fp, bp, f32, fp, ip, bp],
+      'sag_lidar_cost_device': [vp, i32, i32, vp, vp, vp, f32, vp, vp, vp],
+      'sag_set_seed': [vp, u64],
+      'sag_dev_alloc': [vp, u64, C.POINTER(vp)],
+      'sag_dev_free': [vp, vp],
+      'sag_dev_upload': [vp, vp, vp, u64],
+      'sag_dev_download': [vp, vp, vp, u64],
+      'sag_dev_fill_actions': [vp, vp, u32],
+      'sag_kernel_time_ms': [vp, i32, dp, C.POINTER(C.c_int64)],
+      'sag_enable_timing': [vp, i32],
+      'sag_busy_count': [vp, ip],
+      'sag_debug_cycles': [vp, i32, u64p, i32],
+      'sag_debug_doggo_coop': [vp, dp],
+      'sag_render_rgb': [vp, bp],
+      'sag_render_rgb_device': [vp, vp],
+      'sag_render': [vp, i32, i32, i32, i32, bp],
+      'sag_render_device': [vp, i32, i32, i32, i32, vp, vp, vp],
+      'sag_render_rows_device': [vp, i32, i32, i32, i32, vp, vp, vp, vp],
+      'sag_render_envs': [vp, i32, i32, i32, i32, ip, i32, bp],
+      'sag_render_aux': [vp, i32, i32, i32, i32, i32, ip, i32, vp],
+      'sag_render_aux_device': [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp],
+      'sag_device_count': [],
+      'sag_world_config_default': ([cfg], None),
+      'sag_task_desc_default': [i32, task],
+      'sag_task_desc_check': ([task], C.c_char_p),
+      'sag_sample_layouts': [i32, i32, up, ip] + sample_tail,
+      'sag_sample_layouts_desc': [i32, i32, up, task, i32, ip] + sample_tail,
+      'sag_set_tasks': [vp, vp, i32, ip, cfg, i32],
+      'sag_reset_device': [vp, i32, i32, vp, ip, fp],
+      'sag_reset_device_async': [vp, vp, vp],
+      'sag_reset_device_counts': [vp, i32, u64p, u64p],
+      'sag_episode_track_device': [vp, vp, vp, vp, vp, i32, vp, vp],
+      'sag_episode_clear': [vp, vp],
+      'sag_copy_rows_device': [vp, vp, i32, vp, vp],
+      'sag_append_rows_device': [vp, vp, i32, vp, vp, i32, vp, i32, vp],
+      'sag_fork_device': [vp, vp, vp, i32],
+      'sag_fork_counts': [vp, i32, u64p, u64p],
+      'sag_wait_for': [vp, vp],
+      'sag_plan_sample_device': [vp, i32, i32, vp, vp, u32, vp],
+      'sag_plan_score_device': [vp, vp, i32, f32, vp],
+      'sag_plan_refit_device': [vp, i32, i32, i32, vp, vp, vp, f32, vp, vp, vp, vp],
+      'sag_plan_shift_device': [vp, i32, i32, vp, vp, f32],
+      'sag_plan_clear_device': [vp, i32, i32, vp, vp, vp, f32],
+      'sag_gae_device': [vp, C.POINTER(GaeDesc)],
+      'sag_policy_forward_device': [vp, C.POINTER(PolicyDesc)],
+      'sag_policy_backward_device': [vp, C.POINTER(PolicyGradDesc)],
+      'sag_adam_device': [vp, C.POINTER(AdamDesc)],
+      'sag_moments_device': [vp, C.POINTER(MomentsDesc)],
+      'sag_advantage_mix_device': [vp, C.POINTER(AdvantageMixDesc)],
+      'sag_lagrange_device': [vp, C.POINTER(LagrangeDesc)],
+      'sag_grad_clip_device': [vp, C.POINTER(GradClipDesc)],
+      'sag_obs_stats_device': [vp, C.POINTER(ObsStatsDesc)],
+      'sag_policy_forward_norm_device': [vp, C.POINTER(PolicyDesc), vp, f32],
+      'sag_policy_backward_norm_device': [vp, C.POINTER(PolicyGradDesc), vp, f32],
+      'sag_permutation_device': [vp, i32, u32, vp],
+      'sag_policy_backward_rows_device': [vp, C.POINTER(PolicyGradDesc), vp, i32, vp, f32],
+  }
+  return {k: v if isinstance(v, tuple) else (v, C.c_int) for k, v in sigs.items()}   # (a bare list returns the status int)
+
+
+SIGNATURES = _signatures()
+EXPORTS = list(SIGNATURES)
+_lib = None
+
+
+def load():
+  """Load libsag.so; raises SagError (never falls back) if it is not there."""
+  global _lib
+  if _lib is not None:
+    return _lib
+  if not os.path.exists(LIB_PATH):
+    raise SagError(
+        f'{LIB_PATH} not found: build it with `python -m safe_adaptation_gym_amd.build` '
+        '(hipcc, --offload-arch=gfx950). There is no CPU fallback.')
+  lib = C.CDLL(LIB_PATH)
+  # (a SAG_LIB library of an earlier commit lacks some symbols: it still loads for an A/B run of the paths it has, and a call of
+  # a missing one raises AttributeError)
+  for name, (argtypes, restype) in SIGNATURES.items():
+    if hasattr(lib, name):
+      fn = getattr(lib, name)
+      fn.argtypes, fn.restype = argtypes, restype
+  _lib = lib
+  return lib
+
+
+def robot_info(robot):
+  lib = load()
+  out = (C.c_int32 * 5)()
+  dt = C.c_double()
+  rc = lib.sag_robot_info(ROBOT_IDS[robot] if isinstance(robot, str) else robot, out, C.byref(dt))
+  if rc:
+    raise SagError(f'sag_robot_info failed ({rc})')
+  return dict(nu=out[0], obs_dim=out[1], nstep=out[2], nq=out[3], nv=out[4], dt=dt.value)
+
+
 def task_desc_default(task_id):
   """The descriptor the library holds for one of the reference's 14 tasks (what the Python Task classes are tested against)."""
-  lib = load()
-  lib.sag_task_desc_default.argtypes = [C.c_int32, C.POINTER(TaskDesc)]
   t = TaskDesc()
-  if lib.sag_task_desc_default(int(task_id), C.byref(t)) != 0:
+  if load().sag_task_desc_default(int(task_id), C.byref(t)) != 0:
     raise SagError(f'no task {task_id}')
   return t.to_dict()
 
 
 def task_desc_check(desc):
   """None, or what the library objects to in a descriptor dict (the field's name and the rule: include/sag.h)."""
-  lib = load()
-  lib.sag_task_desc_check.argtypes = [C.POINTER(TaskDesc)]
-  lib.sag_task_desc_check.restype = C.c_char_p
-  msg = lib.sag_task_desc_check(C.byref(TaskDesc.from_dict(desc)))
+  msg = load().sag_task_desc_check(C.byref(TaskDesc.from_dict(desc)))
   return None if msg is None else msg.decode()
 
 
@@ -335,10 +331,15 @@ def _ptr(a, ctype):
   return None if a is None else a.ctypes.data_as(C.POINTER(ctype))
 
 
+def _addr(p):
+  """What a descriptor's pointer field takes: the address in a c_void_p; an int or None as it is."""
+  return p.value if isinstance(p, C.c_void_p) else p
+
+
 class DeviceArray:
   """A view of device memory owned by a Context (the outputs of a device-resident env.step, BatchedSafeAdaptationGym
-  with device_buffers=True): pointer, shape, dtype, strides.  `__cuda_array_interface__` (version 2; HIP pointers are
-  what PyTorch-ROCm and CuPy-ROCm expect there) lets a learner wrap it without a copy - torch.as_tensor(a, device='cuda')
+  with device_buffers=True): pointer, shape, dtype, strides.  It exports the CUDA array interface (version 2; HIP pointers are
+  what PyTorch-ROCm and CuPy-ROCm expect there), so a learner wraps it without a copy - torch.as_tensor(a, device='cuda')
   -; `numpy()` downloads.  The memory is written on the context's stream: read it after env.wait() (or step(sync=True))."""
 
   def __init__(self, ctx, ptr, shape, dtype, strides=None, base=None):
@@ -359,33 +360,118 @@ class DeviceArray:
     return np.lib.stride_tricks.as_strided(full.reshape(-1)[off:], self.shape, self.strides).copy()
 
 
+def is_device_array(x):
+  """Whether device_view() reads x: a DeviceArray, or a torch / cupy array on the GPU."""
+  return isinstance(x, DeviceArray) or hasattr(x, '__cuda_array_interface__')
+
+
+@functools.lru_cache(maxsize=1024)
+def _dense_strides(shape, itemsize):
+  strides = []
+  for n in reversed(shape):
+    strides.append(itemsize)
+    itemsize *= max(n, 1)
+  return tuple(reversed(strides))
+
+
+def dense_strides(shape, dtype):
+  """The strides in bytes of a C-contiguous array of that shape, as NumPy forms them; an axis of length 0 counts as 1, so an
+  empty array keeps the strides of its rows.  (Cached: the learner's enqueue path asks for the same few shapes on every call.)"""
+  return _dense_strides(tuple(shape), (dtype if isinstance(dtype, np.dtype) else np.dtype(dtype)).itemsize)
+
+
+class DeviceView(collections.namedtuple('DeviceView', 'ptr shape strides dtype device')):
+  """What device_view() makes of a device array: ptr (int), shape (tuple), strides (bytes, always concrete: the dense ones
+  where the array names none), dtype (np.dtype), device (the index of the GPU the array says it lives on, or None)."""
+  __slots__ = ()
+
+  @property
+  def contiguous(self):
+    return self.strides == dense_strides(self.shape, self.dtype)
+
+
+def device_view(x, what='device array', device=None):
+  """The one reader of device arrays: a DeviceArray, or anything that exports __cuda_array_interface__ (a torch / cupy
+  array on the GPU), as a DeviceView; TypeError for anything else.  `what` starts the messages.  With `device`, the index of
+  the GPU the caller's context runs on, an array that names another one - torch's .device.index, cupy's .device.id, a
+  DeviceArray's context - raises ValueError before a kernel can be handed its pointer.  Every entry point puts its own
+  conditions (dtype, shape, pitch, alignment) on the record."""
+  if isinstance(x, DeviceArray):
+    ptr, shape, strides, dtype, where = x.ptr, x.shape, x.strides, x.dtype, getattr(x.ctx, 'device', None)
+  else:
+    cai = getattr(x, '__cuda_array_interface__', None)
+    if cai is None:
+      raise TypeError(f'{what}: {type(x).__name__} is not a device array')
+    ptr, shape, strides, dtype = int(cai['data'][0]), tuple(cai['shape']), cai.get('strides'), np.dtype(cai['typestr'])
+    dev = getattr(x, 'device', None)   # torch.device (.index) / cupy Device (.id); the interface itself names none
+    where = getattr(dev, 'index', getattr(dev, 'id', None))
+  if not isinstance(where, int):
+    where = None
+  elif device is not None and where != device:
+    raise ValueError(f'{what} on device {where}: this shard runs on device {device}')
+  # (tuple.__new__: the record is built on every enqueue, and a namedtuple's own constructor costs three times as much)
+  return tuple.__new__(DeviceView, (ptr, shape, dense_strides(shape, dtype) if strides is None else tuple(strides), dtype, where))
+
+
 def device_pointer(x, shape=None, device=None, dtype='<f4'):
-  """Device pointer of a DeviceArray or of anything that exports __cuda_array_interface__ (a torch / cupy array on the GPU).
+  """Device pointer of anything device_view() reads.
   With `shape`, the array is what a step reads as its actions: float32 ('<f4'), exactly that shape, contiguous and - where
   the array says which device it lives on - on `device`.  Anything else raises ValueError before a kernel can read it
   (a float64 tensor would be read as float32 pairs, a short one past its end).  `dtype`: the element type required
   instead of float32 (uint8 for a reset mask)."""
-  if isinstance(x, DeviceArray):
-    typestr, xshape, strides, ptr = x.dtype.str, x.shape, x.strides, x.ptr
-    where = getattr(x.ctx, 'device', None)
-  else:
-    cai = getattr(x, '__cuda_array_interface__', None)
-    if cai is None:
-      raise TypeError(f'{type(x).__name__}: not a device array')
-    typestr, xshape, strides, ptr = cai['typestr'], tuple(cai['shape']), cai.get('strides'), int(cai['data'][0])
-    dev = getattr(x, 'device', None)   # torch.device (.index) / cupy Device (.id); the interface itself names none
-    where = getattr(dev, 'index', getattr(dev, 'id', None))
-  if strides is not None and tuple(strides) != tuple(np.zeros(xshape, np.dtype(typestr)).strides):
+  v = device_view(x, 'device_pointer')
+  if not v.contiguous:
     raise ValueError('device actions must be contiguous')
   if shape is not None:
-    if np.dtype(typestr) != np.dtype(dtype):
-      raise ValueError(f'device actions must be float32 (<f4), not {typestr}' if np.dtype(dtype) == np.dtype('<f4') else
-                       f'device array must be {np.dtype(dtype).str}, not {typestr}')
-    if tuple(xshape) != tuple(shape):
-      raise ValueError(f'device actions of shape {tuple(xshape)}: this shard steps {tuple(shape)}')
-    if device is not None and isinstance(where, int) and where != device:
-      raise ValueError(f'device actions on device {where}: this shard runs on device {device}')
-  return ptr
+    want = np.dtype(dtype)
+    if v.dtype != want:
+      raise ValueError(f'device actions must be float32 (<f4), not {v.dtype.str}' if want == np.dtype('<f4') else
+                       f'device array must be {want.str}, not {v.dtype.str}')
+    if v.shape != tuple(shape):
+      raise ValueError(f'device actions of shape {v.shape}: this shard steps {tuple(shape)}')
+    if device is not None and v.device is not None and v.device != device:
+      raise ValueError(f'device actions on device {v.device}: this shard runs on device {device}')
+  return v.ptr
+
+
+class DeviceBuffers:
+  """The device allocations of one object on one Context, by name: bufs.alloc('mean', nbytes) -> the c_void_p, bufs['mean'],
+  bufs.get('budget'), 'adv' in bufs.  close() frees each exactly once - or not at all once the context is destroyed: there is no
+  handle left to free through - and the object closes itself when it is collected, so an owner's close() is a call of this one and a
+  constructor that fails halfway leaks nothing."""
+
+  def __init__(self, ctx):
+    self.ctx, self._ptrs = ctx, {}
+
+  def alloc(self, name, nbytes, zero=False):
+    """A new allocation under a new name; zero=True fills it with zero bytes."""
+    if name in self._ptrs:
+      raise KeyError(f'device buffer {name!r} exists')
+    p = self._ptrs[name] = self.ctx.dev_alloc(int(nbytes))
+    if zero:
+      self.ctx.dev_upload(p, np.zeros(int(nbytes), np.uint8))
+    return p
+
+  def __getitem__(self, name):
+    return self._ptrs[name]
+
+  def __contains__(self, name):
+    return name in self._ptrs
+
+  def get(self, name, default=None):
+    return self._ptrs.get(name, default)
+
+  def close(self):
+    ptrs, self._ptrs = self._ptrs, {}
+    if getattr(self.ctx, 'h', None):
+      for p in ptrs.values():
+        self.ctx.dev_free(p)
+
+  def __del__(self):
+    try:
+      self.close()
+    except Exception:  # interpreter shutdown
+      pass
 
 
 class Context:
@@ -581,32 +667,40 @@ class Context:
     """sag_gae_device: advantages and returns over T stored steps of [T][pitch] arrays, for the reward channel and (d_cvalue
     given) the cost channel, enqueued on the context stream.  Pointers are c_void_p, ints or None; cost_gamma / cost_lam
     default to gamma / lam."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
     d = GaeDesc(int(T), int(pitch), int(capacity), 0, float(gamma), float(lam), float(gamma if cost_gamma is None else cost_gamma),
-                float(lam if cost_lam is None else cost_lam), *[ptr(x) for x in (d_reward, d_cost, d_ended, d_value, d_cvalue, d_slot,
+                float(lam if cost_lam is None else cost_lam), *[_addr(x) for x in (d_reward, d_cost, d_ended, d_value, d_cvalue, d_slot,
                                                                                  d_final_value, d_final_cvalue, d_adv, d_ret, d_cadv, d_cret)])
     self._check(self.lib.sag_gae_device(self.h, C.byref(d)), 'sag_gae_device')
+
+  def _policy_desc(self, n_rows, hidden, d_params, d_obs, logp_const, d_actions, d_logp, d_value, d_cvalue, activation, flags, draw, row0,
+                   obs_pitch):
+    return PolicyDesc(int(n_rows), int(hidden), int(activation), int(flags), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), 0,
+                      int(draw) & 0xffffffff, int(row0) & 0xffffffff, float(logp_const),
+                      *[_addr(x) for x in (d_params, d_obs, d_actions, d_logp, d_value, d_cvalue)])
+
+  def _policy_grad_desc(self, n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale, d_cadv,
+                        d_cret, clip, vf_coef, cvf_coef, ent_coef, adv_affine, cadv_affine, activation, flags, max_blocks, obs_pitch):
+    return PolicyGradDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(hidden),
+                          int(activation), int(flags), int(max_blocks), float(clip), float(vf_coef), float(cvf_coef), float(ent_coef),
+                          float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
+                          *[_addr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
 
   def policy_forward(self, n_rows, hidden, d_params, d_obs, logp_const=0.0, d_actions=None, d_logp=None, d_value=None, d_cvalue=None,
                      activation=POLICY_RELU, flags=0, draw=0, row0=0, obs_pitch=None):
     """sag_policy_forward_device: the fused actor-critic forward of n_rows observation rows (obs_pitch floats apart; default
     obs_dim) under the parameters at d_params (the header has their layout and the arithmetic), enqueued on the context stream
     - no wait, no host copy.  Pointers are c_void_p, ints or None; an output that is None is not written."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    d = PolicyDesc(int(n_rows), int(hidden), int(activation), int(flags), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), 0,
-                   int(draw) & 0xffffffff, int(row0) & 0xffffffff, float(logp_const),
-                   *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp, d_value, d_cvalue)])
+    d = self._policy_desc(n_rows, hidden, d_params, d_obs, logp_const, d_actions, d_logp, d_value, d_cvalue, activation, flags, draw, row0,
+                          obs_pitch)
     self._check(self.lib.sag_policy_forward_device(self.h, C.byref(d)), 'sag_policy_forward_device')
 
   def policy_forward_norm(self, n_rows, hidden, d_params, d_obs, d_table, clip=10.0, logp_const=0.0, d_actions=None, d_logp=None,
                           d_value=None, d_cvalue=None, activation=POLICY_RELU, flags=0, draw=0, row0=0, obs_pitch=None):
     """sag_policy_forward_norm_device: policy_forward with every observation element replaced, where its row is staged, by
     clamp((x - mean) * rstd, -clip, clip) under d_table = mean [obs_dim] then rstd [obs_dim] (what obs_stats writes)."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    d = PolicyDesc(int(n_rows), int(hidden), int(activation), int(flags), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), 0,
-                   int(draw) & 0xffffffff, int(row0) & 0xffffffff, float(logp_const),
-                   *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp, d_value, d_cvalue)])
-    self._check(self.lib.sag_policy_forward_norm_device(self.h, C.byref(d), ptr(d_table), float(clip)), 'sag_policy_forward_norm_device')
+    d = self._policy_desc(n_rows, hidden, d_params, d_obs, logp_const, d_actions, d_logp, d_value, d_cvalue, activation, flags, draw, row0,
+                          obs_pitch)
+    self._check(self.lib.sag_policy_forward_norm_device(self.h, C.byref(d), _addr(d_table), float(clip)), 'sag_policy_forward_norm_device')
 
   def policy_backward(self, n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale,
                       d_cadv=None, d_cret=None, clip=0.2, vf_coef=0.5, cvf_coef=0.5, ent_coef=0.0, adv_affine=(1.0, 0.0),
@@ -616,13 +710,10 @@ class Context:
     function; adv_affine = (adv_mul, adv_sub), cadv_affine likewise.  Pointers are c_void_p, ints or None.
     rows=(d_rows, n_index): sag_policy_backward_rows_device - the batch is the n_index logical elements that the device int32
     list at d_rows names, gathered in place."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    d = PolicyGradDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(hidden),
-                       int(activation), int(flags), int(max_blocks), float(clip), float(vf_coef), float(cvf_coef), float(ent_coef),
-                       float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
-                       *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
+    d = self._policy_grad_desc(n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale, d_cadv,
+                               d_cret, clip, vf_coef, cvf_coef, ent_coef, adv_affine, cadv_affine, activation, flags, max_blocks, obs_pitch)
     if rows is not None:
-      self._check(self.lib.sag_policy_backward_rows_device(self.h, C.byref(d), ptr(rows[0]), int(rows[1]), None, 0.0),
+      self._check(self.lib.sag_policy_backward_rows_device(self.h, C.byref(d), _addr(rows[0]), int(rows[1]), None, 0.0),
                   'sag_policy_backward_rows_device')
       return
     self._check(self.lib.sag_policy_backward_device(self.h, C.byref(d)), 'sag_policy_backward_device')
@@ -634,69 +725,59 @@ class Context:
     """sag_policy_backward_norm_device: policy_backward over observations normalised under d_table and clamped to
     +-obs_clip where they are staged, as policy_forward_norm does.  rows=(d_rows, n_index): sag_policy_backward_rows_device
     with the table."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    d = PolicyGradDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(hidden),
-                       int(activation), int(flags), int(max_blocks), float(clip), float(vf_coef), float(cvf_coef), float(ent_coef),
-                       float(adv_affine[0]), float(adv_affine[1]), float(cadv_affine[0]), float(cadv_affine[1]), float(scale), 0.0,
-                       *[ptr(x) for x in (d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_cadv, d_cret, d_grad)])
+    d = self._policy_grad_desc(n_rows, n_planes, pitch, hidden, d_params, d_obs, d_actions, d_logp_old, d_adv, d_ret, d_grad, scale, d_cadv,
+                               d_cret, clip, vf_coef, cvf_coef, ent_coef, adv_affine, cadv_affine, activation, flags, max_blocks, obs_pitch)
     if rows is not None:
-      self._check(self.lib.sag_policy_backward_rows_device(self.h, C.byref(d), ptr(rows[0]), int(rows[1]), ptr(d_table), float(obs_clip)),
+      self._check(self.lib.sag_policy_backward_rows_device(self.h, C.byref(d), _addr(rows[0]), int(rows[1]), _addr(d_table), float(obs_clip)),
                   'sag_policy_backward_rows_device')
       return
-    self._check(self.lib.sag_policy_backward_norm_device(self.h, C.byref(d), ptr(d_table), float(obs_clip)), 'sag_policy_backward_norm_device')
+    self._check(self.lib.sag_policy_backward_norm_device(self.h, C.byref(d), _addr(d_table), float(obs_clip)), 'sag_policy_backward_norm_device')
 
   def permutation(self, n, draw, d_index):
     """sag_permutation_device: d_index[0 ... n) (device int32) = a keyed pseudo-random permutation of 0 ... n - 1 under the
     context key and `draw` (the header defines it bit for bit); enqueued on the context stream - no wait, no host copy."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    self._check(self.lib.sag_permutation_device(self.h, int(n), int(draw) & 0xffffffff, ptr(d_index)), 'sag_permutation_device')
+    self._check(self.lib.sag_permutation_device(self.h, int(n), int(draw) & 0xffffffff, _addr(d_index)), 'sag_permutation_device')
 
   def obs_stats(self, d_state, d_table, d_obs=None, n_rows=0, n_planes=0, pitch=0, obs_pitch=None, eps=1e-8, max_blocks=0, table_only=False):
     """sag_obs_stats_device: the per-column moments of n_planes x n_rows observation rows (planes `pitch` rows, rows obs_pitch
     floats apart) merged into d_state = {count, mean [obs_dim], M2 [obs_dim]} float64, and d_table = mean, rstd float32 made from
     it; table_only=True rewrites the table from the state and reads no observations.  Enqueued on the context stream."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
     d = ObsStatsDesc(int(n_rows), int(n_planes), int(pitch), int(self.info['obs_dim'] if obs_pitch is None else obs_pitch), int(max_blocks),
-                     OBS_STATS_TABLE_ONLY if table_only else 0, float(eps), 0.0, ptr(d_obs), ptr(d_state), ptr(d_table))
+                     OBS_STATS_TABLE_ONLY if table_only else 0, float(eps), 0.0, _addr(d_obs), _addr(d_state), _addr(d_table))
     self._check(self.lib.sag_obs_stats_device(self.h, C.byref(d)), 'sag_obs_stats_device')
 
   def adam(self, n, d_param, d_grad, d_m, d_v, step, beta1=0.9, beta2=0.999, eps=1e-8, clamp_first=None, clamp_lo=0.0):
     """sag_adam_device: one Adam step on n float32 elements (the header has the chain; `step` is the bias-corrected learning
     rate), elements from clamp_first on kept at or above clamp_lo; enqueued on the context stream."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
     d = AdamDesc(int(n), int(n if clamp_first is None else clamp_first), float(beta1), float(beta2), float(eps), float(step),
-                 float(clamp_lo), 0.0, *[ptr(x) for x in (d_param, d_grad, d_m, d_v)])
+                 float(clamp_lo), 0.0, *[_addr(x) for x in (d_param, d_grad, d_m, d_v)])
     self._check(self.lib.sag_adam_device(self.h, C.byref(d)), 'sag_adam_device')
 
   def moments(self, n_rows, n_planes, pitch, d_x, d_out, d_mask=None, stride=1, eps=1e-8, max_blocks=0):
     """sag_moments_device: d_out[4] = {count, mean, var, 1 / (sqrt(var) + eps)} of the n_planes x n_rows elements of d_x (planes
     `pitch` rows apart, elements `stride` floats apart) whose byte of d_mask [n_planes][pitch] is non-zero (None: all); enqueued
     on the context stream, the result stays on the device."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    d = MomentsDesc(int(n_rows), int(n_planes), int(pitch), int(stride), int(max_blocks), 0, float(eps), 0.0, ptr(d_x), ptr(d_mask), ptr(d_out))
+    d = MomentsDesc(int(n_rows), int(n_planes), int(pitch), int(stride), int(max_blocks), 0, float(eps), 0.0, _addr(d_x), _addr(d_mask), _addr(d_out))
     self._check(self.lib.sag_moments_device(self.h, C.byref(d)), 'sag_moments_device')
 
   def advantage_mix(self, n_rows, n_planes, pitch, d_adv, d_out, d_cadv=None, adv_mode=ADV_RAW, cadv_mode=ADV_RAW, d_adv_mom=None,
                     d_cadv_mom=None, d_lambda=None, cost_weight=0.0):
     """sag_advantage_mix_device: d_out = norm(adv) - lambda * norm(cadv) elementwise (the header has the chain), the moments
     arrays as moments() writes them, lambda = d_lambda[0] or cost_weight; enqueued on the context stream."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
     d = AdvantageMixDesc(int(n_rows), int(n_planes), int(pitch), 0, int(adv_mode), int(cadv_mode), float(cost_weight), 0.0,
-                         *[ptr(x) for x in (d_adv, d_cadv, d_adv_mom, d_cadv_mom, d_lambda, d_out)])
+                         *[_addr(x) for x in (d_adv, d_cadv, d_adv_mom, d_cadv_mom, d_lambda, d_out)])
     self._check(self.lib.sag_advantage_mix_device(self.h, C.byref(d)), 'sag_advantage_mix_device')
 
   def lagrange(self, d_mom, d_state, lr, budget, lambda_max=float('inf')):
     """sag_lagrange_device: d_state[4] = {lambda, mean cost, episodes, updates} takes one step lambda += lr * (mean - budget),
     kept in [0, lambda_max], from the moments at d_mom (no step where their count is 0); enqueued on the context stream."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    d = LagrangeDesc(float(lr), float(budget), float(lambda_max), 0.0, ptr(d_mom), ptr(d_state))
+    d = LagrangeDesc(float(lr), float(budget), float(lambda_max), 0.0, _addr(d_mom), _addr(d_state))
     self._check(self.lib.sag_lagrange_device(self.h, C.byref(d)), 'sag_lagrange_device')
 
   def grad_clip(self, n, d_grad, d_out, max_norm, max_blocks=0):
     """sag_grad_clip_device: d_grad[0 ... n) scaled in place by min(1, max_norm / (norm + 1e-6)), d_out[2] = {norm, factor};
     enqueued on the context stream."""
-    ptr = lambda x: x.value if isinstance(x, C.c_void_p) else x   # noqa: E731
-    d = GradClipDesc(int(n), int(max_blocks), float(max_norm), 0.0, ptr(d_grad), ptr(d_out))
+    d = GradClipDesc(int(n), int(max_blocks), float(max_norm), 0.0, _addr(d_grad), _addr(d_out))
     self._check(self.lib.sag_grad_clip_device(self.h, C.byref(d)), 'sag_grad_clip_device')
 
   def fork_device(self, d_src, source=None, same_stream=False, flags=None):

@@ -100,6 +100,7 @@ class BatchedSafeAdaptationGym:
         nat.Context(self.robot.name, e - s, device=d, seed=0 if device_seed is None else device_seed)
         for (s, e), d in zip(self._ranges, self.devices)
     ]
+    self._own = [nat.DeviceBuffers(c) for c in self._ctx]   # every shard's allocations: _dev, _mask_bufs, _fork_bufs
     self._pool = ThreadPoolExecutor(len(self._ctx)) if len(self._ctx) > 1 else None
     self._dev = None   # device_buffers: per-shard output / action buffers, allocated on first use
     self._tasks = None
@@ -208,7 +209,7 @@ class BatchedSafeAdaptationGym:
 
   def reset(self, *, seed=None, return_info=False, options=None, mask=None, sync=True):
     """mask (device_reset only): the envs to reset - a host bool / uint8 array [n_envs], or one device array of uint8
-    [n_shard] per shard (a DeviceArray such as step()'s `done` view, or any __cuda_array_interface__ array on the shard's
+    [n_shard] per shard (a DeviceArray such as step()'s `done` view, or any torch / cupy array on the shard's
     device; a list when there are several shards).  The other envs keep their state, and their rows of the returned
     observation are what the last step() returned.  A device mask written on another stream must be complete before
     the call (as device actions).
@@ -291,7 +292,7 @@ class BatchedSafeAdaptationGym:
     the best members of a population.  Needs device_reset=True (throughput mode).
 
     src: an int array [n_envs] of global env indices into `source`, negative = keep the env as it is; or, already on the
-    device, one int32 array [n_shard] per shard with shard-LOCAL indices (a DeviceArray or any __cuda_array_interface__
+    device, one int32 array [n_shard] per shard with shard-LOCAL indices (a DeviceArray or any torch / cupy
     array on the shard's device; a list when there are several shards).  A host src is checked before anything is
     launched - ValueError for a wrong shape or dtype, an index out of range, a source that the same call overwrites
     (src[src[i]] must be negative or src[i] itself) and a source on another shard than its destination.  A device src is
@@ -318,7 +319,7 @@ class BatchedSafeAdaptationGym:
     if other is not self and (other._descs != self._descs or
                               bytes(nat.world_config(other.base_config)) != bytes(nat.world_config(self.base_config))):
       raise ValueError('fork(source=...): the envs differ in their task descriptors or world config')
-    on_device = lambda x: isinstance(x, nat.DeviceArray) or hasattr(x, '__cuda_array_interface__')   # noqa: E731
+    on_device = nat.is_device_array
     dsrc = None
     if isinstance(src, (list, tuple)) and len(src) == len(self._ctx) and all(on_device(x) for x in src):
       dsrc = list(src)
@@ -356,7 +357,7 @@ class BatchedSafeAdaptationGym:
       commit.append(ok)
     if dsrc is None:
       if self._fork_bufs is None:
-        self._fork_bufs = [c.dev_alloc(4 * (e - s)) for c, (s, e) in zip(self._ctx, self._ranges)]
+        self._fork_bufs = [o.alloc('fork', 4 * (e - s)) for o, (s, e) in zip(self._own, self._ranges)]
       for c, buf, loc in zip(self._ctx, self._fork_bufs, local):
         c.dev_upload(buf, loc)
       ptrs = [buf.value for buf in self._fork_bufs]
@@ -394,7 +395,7 @@ class BatchedSafeAdaptationGym:
     With device_buffers=True the step is enqueued with sag_step_device and the same tuple comes back as
     _native.DeviceArray views of HBM (obs f32, reward f32, done / cost / goal_met uint8 flags; `bound` stays a host
     array): no copy in either direction.  `action` may be a host array (uploaded) or a device array - a DeviceArray or
-    anything with __cuda_array_interface__, e.g. a torch tensor on the GPU - of shape [N, nu] float32 (one per shard, in
+    anything that exports the CUDA array interface, e.g. a torch tensor on the GPU - of shape [N, nu] float32 (one per shard, in
     a list, when the batch is sharded over several `devices`; the results are then lists, one entry per shard).
     sync=False returns as soon as the launches are enqueued on the contexts' streams: call env.wait() before the
     results are read on another stream.  The views are overwritten by the next step.
@@ -454,20 +455,16 @@ class BatchedSafeAdaptationGym:
     if self._dev is None:
       self._dev = []
       od, nu = self.robot.obs_dim, self.robot.nu
-      for c, (s, e) in zip(self._ctx, self._ranges):
+      for own, (s, e) in zip(self._own, self._ranges):
         n = e - s
-        b = {'act': c.dev_alloc(n * nu * 4), 'obs': c.dev_alloc(n * od * 4), 'rew': c.dev_alloc(n * 2 * 4),
-             'cost': c.dev_alloc(n), 'done': c.dev_alloc(n), 'met': c.dev_alloc(n)}
+        sizes = {'act': n * nu * 4, 'obs': n * od * 4, 'rew': n * 2 * 4, 'cost': n, 'done': n, 'met': n}
+        b = {k: own.alloc(k, nbytes) for k, nbytes in sizes.items()}
         if self._track:
-          b['ended'], b['episode'] = c.dev_alloc(n), c.dev_alloc(n * 16)
-          c.dev_upload(b['ended'], np.zeros(n, np.uint8))
-          c.dev_upload(b['episode'], np.zeros((n, 4), np.float32))
+          b['ended'], b['episode'] = own.alloc('ended', n, zero=True), own.alloc('episode', n * 16, zero=True)
         if self._rgb_observation:
-          b['img'] = c.dev_alloc(n * 64 * 64 * 3)
+          b['img'] = own.alloc('img', n * 64 * 64 * 3)
         if self.final_observation:
-          shape, dtype = ((n, 64, 64, 3), np.uint8) if self._rgb_observation else ((n, od), np.float32)
-          b['final'] = c.dev_alloc(int(np.prod(shape)) * np.dtype(dtype).itemsize)
-          c.dev_upload(b['final'], np.zeros(shape, dtype))
+          b['final'] = own.alloc('final', n * 64 * 64 * 3 if self._rgb_observation else n * od * 4, zero=True)
         self._dev.append(b)
     return self._dev
 
@@ -485,7 +482,7 @@ class BatchedSafeAdaptationGym:
 
   def _step_device(self, action, sync):
     bufs = self._dev_bufs()
-    on_device = lambda x: isinstance(x, nat.DeviceArray) or hasattr(x, '__cuda_array_interface__')   # noqa: E731
+    on_device = nat.is_device_array
     if isinstance(action, (list, tuple)) and len(action) == len(self._ctx) and all(on_device(x) for x in action):
       acts = list(action)          # one device array per shard
     elif on_device(action):
@@ -592,16 +589,9 @@ class BatchedSafeAdaptationGym:
     return out
 
   def close(self):
-    for c, b in zip(self._ctx, self._dev or []):
-      for p in b.values():
-        c.dev_free(p)
-    self._dev = None
-    for c, p in zip(self._ctx, self._mask_bufs or []):
-      c.dev_free(p)
-    self._mask_bufs = None
-    for c, p in zip(self._ctx, self._fork_bufs or []):
-      c.dev_free(p)
-    self._fork_bufs = None
+    for own in self._own:
+      own.close()
+    self._dev = self._mask_bufs = self._fork_bufs = None
     for c in self._ctx:
       c.close()
     if self._pool:
@@ -674,7 +664,7 @@ class BatchedSafeAdaptationGym:
   def _mask_ptrs(self, mask):
     """-> (device pointer of every shard's mask bytes, the host mask as uint8 or None); ValueError for anything that is not
     a mask, before anything is reset."""
-    on_device = lambda x: isinstance(x, nat.DeviceArray) or hasattr(x, '__cuda_array_interface__')   # noqa: E731
+    on_device = nat.is_device_array
     if isinstance(mask, (list, tuple)) and len(mask) == len(self._ctx) and all(on_device(x) for x in mask):
       dmasks = list(mask)
     elif on_device(mask):
@@ -691,7 +681,7 @@ class BatchedSafeAdaptationGym:
       return [nat.device_pointer(m, (e - s,), c.device, np.uint8) for c, (s, e), m in zip(self._ctx, self._ranges, dmasks)], None
     # a host mask travels in a buffer of each shard
     if self._mask_bufs is None:
-      self._mask_bufs = [c.dev_alloc(e - s) for c, (s, e) in zip(self._ctx, self._ranges)]
+      self._mask_bufs = [o.alloc('mask', e - s) for o, (s, e) in zip(self._own, self._ranges)]
     for c, (s, e), buf in zip(self._ctx, self._ranges, self._mask_bufs):
       c.dev_upload(buf, hmask[s:e])
     return [buf.value for buf in self._mask_bufs], hmask

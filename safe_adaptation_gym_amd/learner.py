@@ -107,17 +107,15 @@ class PPOLearner:
     self.t = 0   # Adam steps taken
     self._ctx = c = pi._ctx
     n = pi.n_params
-    self._m, self._v = c.dev_alloc(n * 4), c.dev_alloc(n * 4)
-    c.dev_upload(self._m, np.zeros(n, np.float32))
-    c.dev_upload(self._v, np.zeros(n, np.float32))
+    self._own = own = nat.DeviceBuffers(c)
+    self._m, self._v = own.alloc('m', n * 4, zero=True), own.alloc('v', n * 4, zero=True)
     self._words = self._mixed = self._index = None
     if self.shuffle:
-      self._index = c.dev_alloc(buf.T * buf.N * 4)   # [T x N] int32: the epoch's permutation
+      self._index = own.alloc('index', buf.T * buf.N * 4)   # [T x N] int32: the epoch's permutation
     if self.normalize_advantage or self.max_grad_norm is not None or self.cost_budget is not None:
-      self._words = c.dev_alloc(_WORDS * 4)
-      c.dev_upload(self._words, np.zeros(_WORDS, np.float32))
+      self._words = own.alloc('words', _WORDS * 4, zero=True)
     if self._mixes():
-      self._mixed = c.dev_alloc(buf.T * buf.P * 4)   # [T][P]: the advantage the backward pass is given
+      self._mixed = own.alloc('mixed', buf.T * buf.P * 4)   # [T][P]: the advantage the backward pass is given
     self.cost_weight = float(cost_weight)
 
   def _mixes(self):
@@ -222,16 +220,5 @@ class PPOLearner:
     return stats
 
   def close(self):
-    c = getattr(self, '_ctx', None)
-    if c is not None and c.h:
-      for p in (getattr(self, '_m', None), getattr(self, '_v', None), getattr(self, '_words', None), getattr(self, '_mixed', None),
-                getattr(self, '_index', None)):
-        if p is not None:
-          c.dev_free(p)
+    self._own.close()
     self._m = self._v = self._words = self._mixed = self._index = self._ctx = None
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # interpreter shutdown
-      pass

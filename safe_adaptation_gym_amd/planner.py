@@ -64,10 +64,10 @@ class ShootingPlanner:
     rf, ri = np.repeat(rf, K, axis=0), np.repeat(ri, K, axis=0)
     ri[:, nat.I_ENV_ID] = np.arange(n)
     self._ctx = c = nat.Context(env.robot.name, n, device=self._src_ctx.device, seed=self._key())
-    self._bufs = {}
+    self._bufs = nat.DeviceBuffers(c)
     try:
       c.set_layout(rf, ri)
-      alloc = lambda k, nbytes: self._bufs.setdefault(k, c.dev_alloc(nbytes))   # noqa: E731
+      alloc = self._bufs.alloc
       alloc('src', 4 * n); alloc('plans', 4 * H * n * nu); alloc('mean', 4 * H * G * nu); alloc('sigma', 4 * H * G * nu)
       alloc('score', 16 * n); alloc('best', 4 * G); alloc('best_score', 16 * G); alloc('mask', G)
       if budget is not None:
@@ -141,7 +141,7 @@ class ShootingPlanner:
     c, b = self._ctx, self._bufs
     d_mask = None
     if mask is not None:
-      if isinstance(mask, nat.DeviceArray) or hasattr(mask, '__cuda_array_interface__'):
+      if nat.is_device_array(mask):
         d_mask = nat.C.c_void_p(nat.device_pointer(mask, (self.G,), c.device, np.uint8))
       else:
         m = np.asarray(mask)
@@ -156,15 +156,5 @@ class ShootingPlanner:
     self._ctx.wait()
 
   def close(self):
-    c = getattr(self, '_ctx', None)
-    if c is not None and c.h:
-      for p in self._bufs.values():
-        c.dev_free(p)
-      self._bufs = {}
-      c.close()
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # interpreter shutdown
-      pass
+    self._bufs.close()
+    self._ctx.close()

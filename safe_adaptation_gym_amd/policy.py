@@ -15,6 +15,7 @@ from safe_adaptation_gym_amd import _native as nat
 
 ACTIVATIONS = {'relu': nat.POLICY_RELU, 'tanh': nat.POLICY_TANH}
 KEYS = ('W1', 'b1', 'W2', 'b2', 'W3', 'b3', 'std')
+F32, I32 = np.dtype('<f4'), np.dtype('<i4')
 
 
 def plane_range(view, t0, t1):
@@ -23,7 +24,7 @@ def plane_range(view, t0, t1):
   t0, t1 = int(t0), int(t1)
   if not 0 <= t0 < t1 <= view.shape[0]:
     raise ValueError(f'plane_range: planes {t0} ... {t1} of {view.shape[0]}')
-  strides = view.strides if view.strides is not None else np.zeros(view.shape, view.dtype).strides
+  strides = view.strides if view.strides is not None else nat.dense_strides(view.shape, view.dtype)
   return type(view)(view.ctx, view.ptr + t0 * strides[0], (t1 - t0,) + tuple(view.shape[1:]), view.dtype, strides=tuple(strides),
                     base=view._base)
 
@@ -82,12 +83,13 @@ class MLPPolicy:
     self.draw = 0   # counter word 1 of the next sampled forward
     self.shapes = {'W1': (od, H), 'b1': (H,), 'W2': (H, H), 'b2': (H,), 'W3': (H, nu + 2), 'b3': (nu + 2,), 'std': (nu,)}
     self.n_params = sum(int(np.prod(s)) for s in self.shapes.values())
-    self._buf = c.dev_alloc(self.n_params * 4)
+    self._own = own = nat.DeviceBuffers(c)
+    self._buf = own.alloc('params', self.n_params * 4)
     self.params, off = {}, 0
     for k in KEYS:
       self.params[k] = nat.DeviceArray(c, self._buf.value + 4 * off, self.shapes[k], np.float32)
       off += int(np.prod(self.shapes[k]))
-    self._gbuf = c.dev_alloc((self.n_params + nat.POLICY_GRAD_STATS) * 4)
+    self._gbuf = own.alloc('grad', (self.n_params + nat.POLICY_GRAD_STATS) * 4)
     self.grad, off = {}, 0
     for k in KEYS:
       self.grad[k] = nat.DeviceArray(c, self._gbuf.value + 4 * off, self.shapes[k], np.float32)
@@ -101,7 +103,7 @@ class MLPPolicy:
     init['std'] = np.full(nu, np.exp(log_std), np.float32)
     self.set_params(init)
     if self.normalize_observations:
-      self._obs_state, self._obs_table = c.dev_alloc((1 + 2 * od) * 8), c.dev_alloc(2 * od * 4)
+      self._obs_state, self._obs_table = own.alloc('obs_state', (1 + 2 * od) * 8), own.alloc('obs_table', 2 * od * 4)
       self.set_obs_norm(0.0, np.zeros(od), np.zeros(od))   # the empty state: the identity table
 
   # -- parameters ------------------------------------------------------------------------------------------------------
@@ -145,25 +147,17 @@ class MLPPolicy:
   # -- the forward -------------------------------------------------------------------------------------------------------
   def _rows(self, obs):
     """(pointer, rows, pitch in floats) of a device view [rows, obs_dim] float32 whose rows are contiguous."""
-    if isinstance(obs, nat.DeviceArray):
-      typestr, shape, strides, ptr = obs.dtype.str, obs.shape, obs.strides, obs.ptr
-    else:
-      cai = getattr(obs, '__cuda_array_interface__', None)
-      if cai is None:
-        raise TypeError(f'MLPPolicy: {type(obs).__name__} is not a device array')
-      typestr, shape, strides, ptr = cai['typestr'], tuple(cai['shape']), cai.get('strides'), int(cai['data'][0])
-    if np.dtype(typestr) != np.dtype('<f4') or len(shape) != 2 or shape[1] != self.obs_dim:
-      raise ValueError(f'MLPPolicy: observations must be float32 of shape (rows, {self.obs_dim}), not {typestr} {tuple(shape)}')
-    pitch = self.obs_dim * 4 if strides is None else strides[0]
-    if (strides is not None and strides[1] != 4) or pitch < self.obs_dim * 4 or pitch % 16 or ptr % 16:
+    v = nat.device_view(obs, 'MLPPolicy', self._ctx.device)
+    if v.dtype != F32 or len(v.shape) != 2 or v.shape[1] != self.obs_dim:
+      raise ValueError(f'MLPPolicy: observations must be float32 of shape (rows, {self.obs_dim}), not {v.dtype.str} {v.shape}')
+    pitch = v.strides[0]
+    if v.strides[1] != 4 or pitch < self.obs_dim * 4 or pitch % 16 or v.ptr % 16:
       raise ValueError('MLPPolicy: observation rows must be contiguous, 16-byte aligned and a multiple of 16 bytes apart')
-    return ptr, int(shape[0]), pitch // 4
+    return v.ptr, int(v.shape[0]), pitch // 4
 
   def _out(self, x, shape, what):
     if x is None:
       return None
-    if isinstance(x, nat.DeviceArray) and x.strides is not None and tuple(x.strides) == tuple(np.zeros(x.shape, x.dtype).strides):
-      x = nat.DeviceArray(x.ctx, x.ptr, x.shape, x.dtype)
     try:
       return nat.device_pointer(x, shape, self._ctx.device)
     except ValueError as e:
@@ -215,21 +209,14 @@ class MLPPolicy:
   def _planes(self, x, tail, what):
     """(pointer, planes, rows, pitch in rows) of a time-major float32 device view [planes, rows] + tail whose rows are
     contiguous and whose planes are a whole number of rows apart."""
-    if isinstance(x, nat.DeviceArray):
-      typestr, shape, strides, ptr = x.dtype.str, x.shape, x.strides, x.ptr
-    else:
-      cai = getattr(x, '__cuda_array_interface__', None)
-      if cai is None:
-        raise TypeError(f'MLPPolicy.backward: {what}: {type(x).__name__} is not a device array')
-      typestr, shape, strides, ptr = cai['typestr'], tuple(cai['shape']), cai.get('strides'), int(cai['data'][0])
-    if np.dtype(typestr) != np.dtype('<f4') or len(shape) != 2 + len(tail) or tuple(shape[2:]) != tuple(tail):
+    v, tail = nat.device_view(x, f'MLPPolicy.backward: {what}', self._ctx.device), tuple(tail)
+    if v.dtype != F32 or len(v.shape) != 2 + len(tail) or v.shape[2:] != tail:
       raise ValueError(f'MLPPolicy.backward: {what} must be float32 of shape (planes, rows{"".join(", %d" % t for t in tail)}), '
-                       f'not {typestr} {tuple(shape)}')
-    dense = np.zeros((1, 1) + tuple(tail), np.float32).strides[1:]
-    strides = np.zeros(shape, np.float32).strides if strides is None else tuple(strides)
-    if tuple(strides[1:]) != tuple(dense) or strides[0] % dense[0] or strides[0] < shape[1] * dense[0]:
+                       f'not {v.dtype.str} {v.shape}')
+    row = nat.dense_strides((1,) + tail, F32)   # row[0]: the bytes of one row
+    if v.strides[1:] != row or v.strides[0] % row[0] or v.strides[0] < v.shape[1] * row[0]:
       raise ValueError(f'MLPPolicy.backward: {what}: rows must be contiguous and planes a whole number of rows apart')
-    return ptr, int(shape[0]), int(shape[1]), strides[0] // dense[0]
+    return v.ptr, int(v.shape[0]), int(v.shape[1]), v.strides[0] // row[0]
 
   def _row_list(self, rows):
     """(pointer, count) of a row list: a contiguous device int32 view [count], or such a pair itself."""
@@ -237,14 +224,12 @@ class MLPPolicy:
       p, count = rows
       p, count = int(p.value if hasattr(p, 'value') else p), int(count)
     else:
-      try:
-        p = nat.device_pointer(rows)
-      except ValueError as e:
-        raise ValueError(f'MLPPolicy.backward: rows: {e}') from None
-      cai = rows.__cuda_array_interface__
-      if np.dtype(cai['typestr']) != np.dtype('<i4') or len(cai['shape']) != 1:
-        raise ValueError(f"MLPPolicy.backward: rows must be int32 of shape (count,), not {cai['typestr']} {tuple(cai['shape'])}")
-      count = int(cai['shape'][0])
+      v = nat.device_view(rows, 'MLPPolicy.backward: rows', self._ctx.device)
+      if not v.contiguous:
+        raise ValueError('MLPPolicy.backward: rows: the list must be contiguous')
+      if v.dtype != I32 or len(v.shape) != 1:
+        raise ValueError(f'MLPPolicy.backward: rows must be int32 of shape (count,), not {v.dtype.str} {v.shape}')
+      p, count = v.ptr, int(v.shape[0])
     if count < 1 or p % 4:
       raise ValueError(f'MLPPolicy.backward: rows: {count} entries at a pointer that must be 4-byte aligned')
     return p, count
@@ -333,17 +318,5 @@ class MLPPolicy:
     self._ctx.obs_stats(self._obs_state, self._obs_table, eps=self.obs_eps, table_only=True)
 
   def close(self):
-    c = getattr(self, '_ctx', None)
-    if c is not None and c.h and getattr(self, '_buf', None) is not None:
-      c.dev_free(self._buf)
-      for p in (getattr(self, '_gbuf', None), getattr(self, '_obs_state', None), getattr(self, '_obs_table', None)):
-        if p is not None:
-          c.dev_free(p)
-    self._buf = self._gbuf = self._obs_state = self._obs_table = None
-    self._ctx = None
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # interpreter shutdown
-      pass
+    self._own.close()
+    self._buf = self._gbuf = self._obs_state = self._obs_table = self._ctx = None

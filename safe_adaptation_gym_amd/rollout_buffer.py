@@ -25,13 +25,9 @@ class TimeMajorArray(nat.DeviceArray):
     t %= self.shape[0]
     shape, strides = self.shape[1:], tuple(self.strides[1:])
     ptr = self.ptr + t * self.strides[0]
-    if strides == tuple(np.zeros(shape, self.dtype).strides):
+    if strides == nat.dense_strides(shape, self.dtype):
       return nat.DeviceArray(self.ctx, ptr, shape, self.dtype)
     return nat.DeviceArray(self.ctx, ptr, shape, self.dtype, strides=strides, base=self._base)
-
-
-def _on_device(x):
-  return isinstance(x, nat.DeviceArray) or hasattr(x, '__cuda_array_interface__')
 
 
 class RolloutBuffer:
@@ -91,23 +87,22 @@ class RolloutBuffer:
     self.obs_dim, self.nu = env.robot.obs_dim, env.robot.nu
     self._ctx = c = env._ctx[0]
     od, nu = self.obs_dim, self.nu
-    self._bufs = {}
+    self._bufs = nat.DeviceBuffers(c)
     self._t = None         # the step to enqueue next; None before begin()
     self._rollouts = 0
     self._restart = True   # the next append zeroes the store's counter
     try:
-      alloc = lambda k, nbytes: self._bufs.setdefault(k, c.dev_alloc(nbytes))   # noqa: E731
+      alloc = self._bufs.alloc
       alloc('obs', (T + 1) * P * od * 4); alloc('actions', T * P * nu * 4); alloc('reward', T * P * 8)
       for k in ('cost', 'done', 'terminated', 'goal_met'):
         alloc(k, T * P)
       alloc('episode', T * P * 16); alloc('final_slot', T * P * 4)
-      alloc('store', cap * od * 4); alloc('count', 256)
-      c.dev_upload(self._bufs['count'], np.zeros(64, np.int32))
+      alloc('store', cap * od * 4); alloc('count', 256, zero=True)
     except Exception:
       self.close()
       raise
     A = TimeMajorArray
-    b = {k: p.value for k, p in self._bufs.items()}
+    b = {k: self._bufs[k].value for k in ('obs', 'actions', 'reward', 'cost', 'done', 'terminated', 'goal_met', 'episode', 'final_slot')}
     self.obs = A(c, b['obs'], (T + 1, N, od), np.float32, strides=(P * od * 4, od * 4, 4), base=(b['obs'], (T + 1, P, od)))
     self.actions = A(c, b['actions'], (T, N, nu), np.float32, strides=(P * nu * 4, nu * 4, 4), base=(b['actions'], (T, P, nu)))
     self.reward = A(c, b['reward'], (T, N), np.float32, strides=(P * 8, 8), base=(b['reward'], (T, P, 2)))
@@ -124,9 +119,7 @@ class RolloutBuffer:
   def _plane(self, key, shape, dtype=np.float32):
     """An owned [rows][P] (or [rows]) buffer made on first use, zero-filled."""
     if key not in self._bufs:
-      nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
-      self._bufs[key] = self._ctx.dev_alloc(nbytes)
-      self._ctx.dev_upload(self._bufs[key], np.zeros(shape, dtype))
+      self._bufs.alloc(key, int(np.prod(shape)) * np.dtype(dtype).itemsize, zero=True)
     return self._bufs[key]
 
   def _tm(self, key, rows):
@@ -239,17 +232,12 @@ class RolloutBuffer:
     """Device pointer of a [rows][P] value array: host values are uploaded into the owned buffer, a device array must have
     the buffer's pitch (the owned views `value` / `cost_value` have it)."""
     N, P = self.N, self.P
-    if _on_device(x):
-      if isinstance(x, nat.DeviceArray):
-        typestr, shape, strides, ptr = x.dtype.str, x.shape, x.strides, x.ptr
-      else:
-        cai = x.__cuda_array_interface__
-        typestr, shape, strides, ptr = cai['typestr'], tuple(cai['shape']), cai.get('strides'), int(cai['data'][0])
-      strides = (N * 4, 4) if strides is None else tuple(strides)
-      if np.dtype(typestr) != np.dtype('<f4') or tuple(shape) != (rows, N) or strides != (P * 4, 4) or ptr % 4:
+    if nat.is_device_array(x):
+      v = nat.device_view(x, f'RolloutBuffer.advantages: {what}', self._ctx.device)
+      if v.dtype != np.dtype('<f4') or v.shape != (rows, N) or v.strides != (P * 4, 4) or v.ptr % 4:
         raise ValueError(f'RolloutBuffer.advantages: a device {what} must be float32 of shape ({rows}, {N}) with strides '
                          f'({P * 4}, 4) - write into the buffer\'s own view')
-      return nat.C.c_void_p(ptr)
+      return nat.C.c_void_p(v.ptr)
     h = np.asarray(x, np.float32)
     if h.shape != (rows, N):
       raise ValueError(f'RolloutBuffer.advantages: {what} of shape {h.shape}, not ({rows}, {N})')
@@ -260,7 +248,7 @@ class RolloutBuffer:
 
   def _finals(self, key, x, what):
     cap = self.final_capacity
-    if _on_device(x):
+    if nat.is_device_array(x):
       return nat.C.c_void_p(nat.device_pointer(x, (cap,), self._ctx.device))
     h = np.asarray(x, np.float32)
     if h.ndim != 1 or len(h) > cap:
@@ -301,15 +289,5 @@ class RolloutBuffer:
             for k in keys}
 
   def close(self):
-    c = getattr(self, '_ctx', None)
-    if c is not None and c.h:
-      for p in self._bufs.values():
-        c.dev_free(p)
-    self._bufs = {}
+    self._bufs.close()
     self._ctx = None
-
-  def __del__(self):
-    try:
-      self.close()
-    except Exception:  # interpreter shutdown
-      pass
